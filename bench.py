@@ -15,7 +15,11 @@ and the new positions are all-gathered by RCCL over xGMI inside the engine.
     --nproc-per-node N ... bench.py ...` as a CHILD process before anything touches the GPU and
     exits with its status (`--dry-run` prints that command); inside torchrun, WORLD_SIZE must
     equal --gpus, and RCCL's own communicator size (ncclCommCount) must equal it too.
-  * After the timed region every rank checks itself (`--verify`, on by default): the engine is
+  * A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times one bh_step(K) call,
+    writes the final state if `--dump-outputs DIR` is given and prints the line.  Every other
+    leg -- the counting walks and the roofline, GPU clock samples, the one-step-per-call leg,
+    the CPU baseline, rank 0's one-GPU run, the self-check below -- runs only with `--full`.
+  * After the timed region every rank checks itself (`--verify`, on with `--full`): the engine is
     reset to a committed golden configuration -- C4 x 10 steps on N > 1 GPUs (the north-star
     scene through the sharded path), C3 x 10 steps on one GPU -- and the SHA-256 of every final
     SoA field must equal tests/golden/digests.json (made by the CPU oracle) on every rank; a
@@ -68,6 +72,17 @@ def parse():
                          "the north-star 1e7 cloud), c3x (weak scaling: 1e6 bodies per GPU), "
                          "c2, c5 (theta=0 all-pairs), c1_code, c1_baseline")
     ap.add_argument("--theta", type=float, default=None, help="default 0.5 (c5: 0.0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run every other leg: traversal counters and "
+                         "the roofline, GPU clock sampling, the one-step-per-call leg, rank 0's "
+                         "one-GPU run (N > 1), the CPU baseline and the golden-digest self-check "
+                         "(the --no-* options below switch single legs off again); without it "
+                         "the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state they ended in (what "
+                         "bh_get_bodies returns: x, y, vx, vy, m in caller order) as "
+                         "DIR/<name>.npy, float64; of more than 1.5e6 bodies (60 MB), a fixed "
+                         "seeded sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-counters", action="store_true",
                     help="skip the V-bar / lane-efficiency counting walks on the timed state")
@@ -76,7 +91,7 @@ def parse():
     ap.add_argument("--cpu-steps", type=int, default=1)
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--verify", dest="verify", action="store_true", default=None,
-                    help="golden-digest self-check after the timed region (default on)")
+                    help="golden-digest self-check after the timed region (on with --full)")
     ap.add_argument("--no-verify", dest="verify", action="store_false")
     ap.add_argument("--no-single-gpu", action="store_true",
                     help="N > 1: skip rank 0's one-GPU run of the same workload")
@@ -395,6 +410,27 @@ def _sha(a) -> str:
     return hashlib.sha256(np.ascontiguousarray(a, dtype="<f8").tobytes()).hexdigest()
 
 
+DUMP_MAX_BODIES = 1_500_000  # 5 fp64 fields x 1.5e6 bodies = 60 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(path, state):
+    """--dump-outputs: the state the timed steps ended in (bh_get_bodies: caller order, merged
+    bodies removed) as <path>/<field>.npy, float64.  Above DUMP_MAX_BODIES bodies the same
+    seeded sample of the bodies (ascending indices) is written for every field, so two builds
+    run with the same arguments write the same bodies."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = len(state[0])
+    idx = None
+    if n > DUMP_MAX_BODIES:
+        idx = np.sort(np.random.default_rng(1).choice(n, size=DUMP_MAX_BODIES, replace=False))
+    for name, a in zip(FIELDS, state):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a[idx])
+    return {"dir": path, "fields": list(FIELDS), "bodies": n,
+            "written": n if idx is None else DUMP_MAX_BODIES, "dtype": "float64"}
+
+
 def verify_leg(bh_amd, eng, case, arrs, dist, rank, world):
     """Reset the engine to the golden configuration `case` of tests/golden/digests.json, run its
     steps in one bh_step call and compare the SHA-256 of every final SoA field (little-endian
@@ -623,8 +659,10 @@ def main():
     if args.theta is None:
         args.theta = 0.0 if args.config == "c5" else 0.5
     direct = args.theta == 0.0
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_counters = args.no_drop_in = args.no_single_gpu = args.no_cpu_baseline = True
     if args.verify is None:
-        args.verify = True
+        args.verify = args.full
     if args.dry_run:
         print(json.dumps({"launch": "single process, one handle over the GPUs" if single_proc
                           else "in-process", "world": world, "n_gpus": n_gpus,
@@ -686,8 +724,9 @@ def main():
         # the drop-in leg reads the pinned mirror: its stream is made now, right after the
         # engine's own streams and before the counter probe's (hardware queues go out in stream
         # creation order), and the mirror stays off until that leg
-        eng.set_mirror(True)
-        eng.set_mirror(False)
+        if not args.no_drop_in:
+            eng.set_mirror(True)
+            eng.set_mirror(False)
 
     holder["eng"] = eng
     arrs, scene_name, scaling = scene_for(args.config, n_gpus)
@@ -704,7 +743,7 @@ def main():
     if not direct and not args.no_counters and rank == 0:
         cnt_start = traversal_counters(bh_amd, params, local_rank, eng.get_bodies())
 
-    clocks = ClockSampler(local_rank) if rank == 0 else None
+    clocks = ClockSampler(local_rank) if rank == 0 and args.full else None
     set_phase("timed")
     eng.set_profiling(not args.no_events)
     if world > 1:
@@ -745,6 +784,10 @@ def main():
             mine = {k: round(v / max(args.steps, 1), 3) for k, v in m.last_timings().items()}
             mine["let"] = m.let_stats()
             per_rank.append(mine)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # before any other leg moves the state on
+        set_phase("dump outputs")
+        dumped = dump_outputs(args.dump_outputs, eng.get_bodies())
     cnt_end = None
     if not direct and not args.no_counters and rank == 0:
         cnt_end = traversal_counters(bh_amd, params, local_rank, eng.get_bodies())
@@ -843,6 +886,8 @@ def main():
         "gpu_clock": clock_stats,
     }
     roofline.update(extra)
+    if not args.full:  # its inputs (the counting walks, the clock samples) are --full's legs
+        roofline = None
 
     # rank 0's extra legs; the other ranks wait at the next collective
     set_phase("extra legs")
@@ -877,6 +922,7 @@ def main():
             "n_gpus": n_gpus,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True,
             "scaling": scaling,
@@ -906,6 +952,8 @@ def main():
             "cpu_baseline": cpu_baseline,
             "verify": verify,
         }
+        if dumped is not None:
+            line["outputs"] = dumped
         if drop_in is not None:
             line["drop_in"] = drop_in
         if rccl is not None:

@@ -1,6 +1,6 @@
 """bench.py's launch contract on CPU (no GPU is touched): `--gpus N` (N > 1) outside torchrun
 starts torchrun as a child process (shown by --dry-run), a WORLD_SIZE that differs from --gpus is
-refused, and one GPU runs in-process with the golden self-check on."""
+refused, and one GPU runs in-process, with the golden self-check on under --full."""
 import json
 import os
 import subprocess
@@ -36,20 +36,27 @@ def test_world_size_mismatch_is_refused():
 
 
 def test_single_gpu_runs_in_process_with_verification():
-    r = _run(["--dry-run"])
+    r = _run(["--full", "--dry-run"])
     assert r.returncode == 0, r.stderr
     plan = json.loads(r.stdout.strip().splitlines()[-1])
     assert plan == {"launch": "in-process", "world": 1, "n_gpus": 1, "config": "c3",
                     "theta": 0.5, "verify": True}
-    r = _run(["--gpus", "4", "--dry-run"], {"WORLD_SIZE": "4", "RANK": "0", "LOCAL_RANK": "0"})
+    r = _run(["--gpus", "4", "--full", "--dry-run"],
+             {"WORLD_SIZE": "4", "RANK": "0", "LOCAL_RANK": "0"})
     plan = json.loads(r.stdout.strip().splitlines()[-1])
     assert plan["world"] == 4 and plan["config"] == "c4" and plan["verify"] is True
+    # a plain run times the steps only; the self-check can still be asked for by name
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dry-run"])
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip().splitlines()[-1])["verify"] is False
+    r = _run(["--verify", "--dry-run"])
+    assert json.loads(r.stdout.strip().splitlines()[-1])["verify"] is True
 
 
 def test_single_process_multi_gpu_stays_in_process():
     """--single-process: one process, one engine handle over the N GPUs (bh_create_multi), no
     torchrun (the measuring process is a child of the watchdog parent); refused under torchrun."""
-    r = _run(["--gpus", "8", "--single-process", "--dry-run"])
+    r = _run(["--gpus", "8", "--single-process", "--full", "--dry-run"])
     assert r.returncode == 0, r.stderr
     plan = json.loads(r.stdout.strip().splitlines()[-1])
     assert plan["launch"].startswith("single process") and plan["n_gpus"] == 8
@@ -57,6 +64,30 @@ def test_single_process_multi_gpu_stays_in_process():
     r = _run(["--gpus", "4", "--single-process", "--dry-run"],
              {"WORLD_SIZE": "4", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2 and "torchrun" in r.stderr
+
+
+def test_dump_outputs_writes_the_fields_and_samples_large_states(tmp_path, monkeypatch):
+    """--dump-outputs: every field of the final state as float64 <field>.npy; above the body
+    limit the same seeded sample of the bodies for every field, the same from run to run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 1000
+    state = tuple(np.arange(n, dtype=np.float64) + 10000.0 * k for k in range(5))
+    info = bench.dump_outputs(str(tmp_path / "whole"), state)
+    assert info["written"] == n and info["bodies"] == n
+    for k, f in enumerate(bench.FIELDS):
+        a = np.load(tmp_path / "whole" / f"{f}.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, state[k])
+    assert bench.DUMP_MAX_BODIES * 8 * len(bench.FIELDS) + 5 * 128 <= 64 * 1000 * 1000
+    monkeypatch.setattr(bench, "DUMP_MAX_BODIES", 100)
+    bench.dump_outputs(str(tmp_path / "a"), state)
+    bench.dump_outputs(str(tmp_path / "b"), state)
+    xa = np.load(tmp_path / "a" / "x.npy")
+    assert xa.shape == (100,) and np.all(np.diff(xa) > 0)
+    for k, f in enumerate(bench.FIELDS):
+        a, b = np.load(tmp_path / "a" / f"{f}.npy"), np.load(tmp_path / "b" / f"{f}.npy")
+        assert np.array_equal(a, b) and np.array_equal(a - 10000.0 * k, xa)  # the same bodies
 
 
 _DUMMY_WORKER = """

@@ -7,7 +7,7 @@ set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 ROUNDS=${ROUNDS:-3}
-ARGS=${AB_ARGS:-"--steps 10 --warmup 2 --no-cpu-baseline"}
+ARGS=${AB_ARGS:-"--full --steps 10 --warmup 2 --no-cpu-baseline"}
 for r in $(seq 1 $ROUNDS); do
   for L in ${LIBS:-A B}; do
     BH_ENGINE_LIB=$PWD/barnes-hut-n-body_amd/lib/lib$L.so timeout -k 10 300 python bench.py $ARGS \

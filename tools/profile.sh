@@ -9,8 +9,8 @@ CONFIG=${CONFIG:-c3}
 OUT=gpurun_out/prof_$CONFIG
 mkdir -p $OUT
 STEPS=${STEPS:-10}
-ARGS="--config $CONFIG --steps $STEPS --warmup 2 --no-cpu-baseline"
-PMC_ARGS="--config $CONFIG --steps 2 --warmup 1 --no-cpu-baseline"
+ARGS="--full --config $CONFIG --steps $STEPS --warmup 2 --no-cpu-baseline"
+PMC_ARGS="--full --config $CONFIG --steps 2 --warmup 1 --no-cpu-baseline"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run --output-format csv \
   -- python3 bench.py $ARGS > $OUT/trace.log 2>&1 || { echo "trace rc=$?"; exit 1; }
 echo "trace ok"; tail -1 $OUT/trace.log | cut -c1-400

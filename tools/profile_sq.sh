@@ -7,7 +7,7 @@ OUT=gpurun_out/prof_sq
 mkdir -p $OUT
 # CONFIG=c2 etc. for another workload; SQ_CACHE=1 adds a pass of scalar-cache and L2 hit counters
 timeout -k 10 120 rocprofv3 -L > $OUT/counters.txt 2>&1 || true
-ARGS="--config ${CONFIG:-c3} --steps 2 --warmup 1 --no-cpu-baseline"
+ARGS="--full --config ${CONFIG:-c3} --steps 2 --warmup 1 --no-cpu-baseline"
 i=0
 for SET in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE" \
            "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVES" \

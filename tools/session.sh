@@ -6,7 +6,7 @@
 # Steps (outputs under gpurun_out/, prefixed with $TAG):
 #   tests          python -m pytest tests -m gpu (PYTEST_K="expr" narrows it)  -> ${TAG}_pytest.log
 #   smoke          __graft_entry__.smoke()                                     -> ${TAG}_smoke.log
-#   bench          the driver's command: bench.py --steps 20 --warmup 5        -> ${TAG}_bench_lines.jsonl
+#   bench          every leg of the bench: bench.py --full --steps 20 --warmup 5      -> ${TAG}_bench_lines.jsonl
 #   configs        one bench line per BASELINE configuration (c1_baseline, c1_code, c2, c4, c5)
 #   profile        rocprofv3 kernel trace + stats and FETCH_SIZE / WRITE_SIZE passes of C3
 #                  (tools/profile.sh; CONFIG=c5 etc. for another workload) -> prof_<CONFIG>/
@@ -52,10 +52,10 @@ for step in "$@"; do
       run ${PYTEST_TIMEOUT:-1200} ${O}_pytest.log python -u -m pytest tests -m gpu -x -v \
         --timeout 300 --timeout-method thread ${PYTEST_K:+-k "$PYTEST_K"} ;;
     smoke) run 300 ${O}_smoke.log python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) bench_line --steps 20 --warmup 5 ;;
+    bench) bench_line --full --steps 20 --warmup 5 ;;
     configs)
-      for c in c1_baseline c1_code c2 c4; do bench_line --config $c --steps 10 --warmup 2; done
-      bench_line --config c5 --steps 2 --warmup 1 ;;
+      for c in c1_baseline c1_code c2 c4; do bench_line --full --config $c --steps 10 --warmup 2; done
+      bench_line --full --config c5 --steps 2 --warmup 1 ;;
     profile) run 1800 ${O}_profile.log bash tools/profile.sh ;;
     sq)
       run 900 ${O}_sq.log bash tools/profile_sq.sh
@@ -127,9 +127,9 @@ for step in "$@"; do
       for rr in $(seq 1 ${ROUNDS:-2}); do
         for E in ${ENVS:-none}; do
           if [ "$E" = none ]; then
-            run 600 ${O}_envab.log python -u bench.py ${AB_ARGS:---steps 10 --warmup 2 --no-cpu-baseline}
+            run 600 ${O}_envab.log python -u bench.py ${AB_ARGS:---full --steps 10 --warmup 2 --no-cpu-baseline}
           else
-            run 600 ${O}_envab.log env "$E" python -u bench.py ${AB_ARGS:---steps 10 --warmup 2 --no-cpu-baseline}
+            run 600 ${O}_envab.log env "$E" python -u bench.py ${AB_ARGS:---full --steps 10 --warmup 2 --no-cpu-baseline}
           fi
           echo "{\"env\": \"$E\", \"line\": $(grep '^{' ${O}_envab.log | tail -1)}" >> ${O}_envab.jsonl
         done
@@ -141,7 +141,7 @@ for step in "$@"; do
         [ $L = default ] || lib=$PWD/barnes-hut-n-body_amd/lib/lib$L.so
         export BH_ENGINE_LIB=$lib
         run 600 ${O}_kstats_$L.log rocprofv3 --kernel-trace --stats -d ${O}_kstats_$L -o run \
-          --output-format csv -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline \
+          --output-format csv -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline \
           --no-counters --no-drop-in
         unset BH_ENGINE_LIB
       done ;;
