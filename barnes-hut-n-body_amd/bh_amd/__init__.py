@@ -47,7 +47,8 @@ EXPORTED_SYMBOLS = (
     "bh_debug_inject", "bh_set_mirror", "bh_map_bodies", "bh_create_multi",
     "bh_create_multi_list", "bh_multi_world", "bh_multi_member", "bh_collective_log",
     "bh_collective_log_clear", "bh_step_begin", "bh_step_positions", "bh_step_end",
-    "bh_progress",
+    "bh_progress", "bh_compute_potential", "bh_compute_diagnostics", "bh_potential_kernel_ms",
+    "bh_nbody3d_center_of_mass",
 )
 
 
@@ -63,6 +64,52 @@ class BhParams(ctypes.Structure):
         ("merge_max_mass", ctypes.c_double),
         ("merge_min_dist", ctypes.c_double),
     ]
+
+
+class BhDiagnostics(ctypes.Structure):
+    """struct bh_diagnostics (include/bh_engine.h) — the global sums of bh_compute_diagnostics."""
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("mass", ctypes.c_double),
+        ("mx", ctypes.c_double),
+        ("my", ctypes.c_double),
+        ("px", ctypes.c_double),
+        ("py", ctypes.c_double),
+        ("lz", ctypes.c_double),
+        ("kinetic", ctypes.c_double),
+        ("potential", ctypes.c_double),
+    ]
+
+
+@dataclass(frozen=True)
+class Diagnostics:
+    """Engine.diagnostics(): the sums of struct bh_diagnostics plus the derived quantities.
+    `potential` is 0.5 * sum m * phi, or 0.0 when it was not asked for."""
+    n: int
+    mass: float
+    mx: float
+    my: float
+    px: float
+    py: float
+    lz: float
+    kinetic: float
+    potential: float
+
+    @property
+    def com(self):
+        """Centre of mass (sum m x / sum m, sum m y / sum m); (0, 0) if the total mass is 0."""
+        if self.mass == 0.0:
+            return (0.0, 0.0)
+        return (self.mx / self.mass, self.my / self.mass)
+
+    @property
+    def momentum(self):
+        return (self.px, self.py)
+
+    @property
+    def energy(self) -> float:
+        """Kinetic + potential energy (kinetic alone without the potential)."""
+        return self.kinetic + self.potential
 
 
 class BhError(RuntimeError):
@@ -129,6 +176,9 @@ def load_library(path: str | None = None):
                                       ctypes.POINTER(ctypes.POINTER(ctypes.c_uint32)), _I64P, _I64P]
     lib.bh_step_end.argtypes = [_VP]
     lib.bh_compute_accelerations.argtypes = [_VP, _D, _D, _I64P]
+    lib.bh_compute_potential.argtypes = [_VP, _D]
+    lib.bh_compute_diagnostics.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(BhDiagnostics)]
+    lib.bh_potential_kernel_ms.argtypes = [_VP, _D]
     lib.bh_get_quads.argtypes = [_VP, _D, _D, _D, ctypes.c_int64, _I64P]
     lib.bh_last_timings.argtypes = [_VP, _D]
     lib.bh_last_tree_nodes.argtypes = [_VP]
@@ -161,6 +211,7 @@ def load_library(path: str | None = None):
                                     ctypes.c_float]
     lib.bh_nbody3d_accelerations.argtypes = [_VP, ctypes.c_float, ctypes.c_float, _F, _F, _F]
     lib.bh_nbody3d_get.argtypes = [_VP] + [_F] * 7 + [ctypes.c_int64, _I64P]
+    lib.bh_nbody3d_center_of_mass.argtypes = [_VP, _D]
     lib.bh_nbody3d_last_ms.argtypes = [_VP]
     lib.bh_nbody3d_last_ms.restype = ctypes.c_double
     lib.bh_scene_galaxy_disk.argtypes = (
@@ -257,6 +308,22 @@ class NBody3D:
         self._check(self._lib.bh_nbody3d_get(self._h, *ptrs, self.n, ctypes.byref(got)),
                     "bh_nbody3d_get")
         return tuple(out)
+
+    def center_of_mass_sums(self):
+        """(sum x m, sum y m, sum z m, sum m) in fp64, reduced on the device
+        (bh_nbody3d_center_of_mass): nothing but these four values is read back."""
+        out = np.zeros(4, dtype=np.float64)
+        self._check(self._lib.bh_nbody3d_center_of_mass(self._h, _dp(out)),
+                    "bh_nbody3d_center_of_mass")
+        return tuple(float(v) for v in out)
+
+    def center_of_mass(self):
+        """GpuNBodyRenderer.computeCenterOfMass() (GPU.kt:390-411): three floats, (0, 0, 0)
+        for an empty or massless set."""
+        sx, sy, sz, sm = self.center_of_mass_sums()
+        if sm == 0.0:
+            return (0.0, 0.0, 0.0)
+        return (sx / sm, sy / sm, sz / sm)
 
     def last_ms(self) -> float:
         return float(self._lib.bh_nbody3d_last_ms(self._h))
@@ -486,6 +553,31 @@ class Engine:
             self._h, _dp(ax), _dp(ay), vis.ctypes.data_as(_I64P) if visits else None))
         return (ax, ay, vis) if visits else (ax, ay)
 
+    def compute_potential(self):
+        """bh_compute_potential: phi per body in caller order.  A build, exactly as
+        compute_accelerations (the jitter may move positions).  An accepted cell that contains
+        the body includes the body's own mass, as its force does; theta = 0 is the exact
+        softened pair potential."""
+        n = max(self.num_bodies(), 0)  # (-1 while a call begun by step_begin runs: refused below)
+        phi = np.empty(n, dtype=np.float64)
+        self._check(self._lib.bh_compute_potential(self._h, _dp(phi)))
+        return phi
+
+    def diagnostics(self, potential: bool = True) -> Diagnostics:
+        """bh_compute_diagnostics: mass, first moments, momentum, angular momentum, kinetic and
+        (potential=True: a build, as compute_potential) potential energy, summed on the device
+        in a fixed order.  potential=False reads the state and changes nothing."""
+        d = BhDiagnostics()
+        self._check(self._lib.bh_compute_diagnostics(self._h, 1 if potential else 0,
+                                                     ctypes.byref(d)))
+        return Diagnostics(int(d.n), d.mass, d.mx, d.my, d.px, d.py, d.lz, d.kinetic, d.potential)
+
+    def potential_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last potential kernel launch (bh_potential_kernel_ms)."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.bh_potential_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def last_removed(self):
         """Indices (list before the last step() call) removed by the merge rule, ascending."""
         need = ctypes.c_int64(0)
@@ -712,6 +804,18 @@ class PhysicsEngine:
         cx, cy, h = self._eng.get_quads()
         self._pull()
         return BHTree(cx, cy, h)
+
+    def diagnostics(self, potential: bool = True) -> Diagnostics:
+        """Conservation read-out of the caller's list (Engine.diagnostics; the reference has
+        none).  potential=True builds a tree as step()'s first half does, so its jitter is
+        written back into the Body objects."""
+        self._eng.set_params(self._params())
+        if self._changed():
+            self._push()
+        d = self._eng.diagnostics(potential)
+        if potential:
+            self._pull()
+        return d
 
     getBodies = get_bodies
     resetBodies = reset_bodies

@@ -559,6 +559,27 @@ hipError_t leaf_list_build(const Node *nodes, const uint32_t *d_T, int64_t node_
 void direct_forces(const LeafList &L, const uint32_t *d_count, const double *x, const double *y,
                    const double *m, int64_t lo, int64_t hi, double G, double soft2, double *a2,
                    hipStream_t s);
+// theta = 0 potential of slots [0, n) over the same leaf sequence, written by slot: bit-identical
+// to potential_walk at theta = 0 (tombstones: phi = 0)
+void direct_potential(const LeafList &L, const uint32_t *d_count, const double *x, const double *y,
+                      const uint32_t *cidx, int64_t n, double G, double soft2, double *phi,
+                      hipStream_t s);
+
+// ---- launchers (potential.hip) ---------------------------------------------------
+// phi[p] = -(G * sum of mass / sqrt(dist2 + soft2)) over the nodes body p's force walk takes
+// (BHA:215-239: massless nodes skipped, the own leaf skipped by identity, an internal node taken
+// iff s2 < theta2 * dist2), added in pre-order from +0.0; an accepted cell that holds p includes
+// p's own mass.  All n lanes, lane q = slot lanes[q] (null: q); phi is written by slot.
+void potential_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const double *x,
+                    const double *y, const uint32_t *cidx, int64_t n, const Geometry &g,
+                    const ForceParams &fp, double *phi, const uint32_t *lanes, hipStream_t s);
+// Fixed-order sums over n bodies (arrays in the caller's list order): out8 = sum of m, m x, m y,
+// m vx, m vy, m (x vy - y vx), 0.5 m (vx vx + vy vy), m phi (0 if phi is null).  No
+// floating-point atomics: per-workgroup partials in `part` (diag_partial_doubles() entries),
+// then one final workgroup.  n = 0: zeros.
+size_t diag_partial_doubles();
+void diag_reduce(int64_t n, const double *x, const double *y, const double *vx, const double *vy,
+                 const double *m, const double *phi, double *part, double *out8, hipStream_t s);
 
 // ---- launchers (integrate.hip) ---------------------------------------------------
 // a2 indexed by traversal lane when lanes != null (lane i holds body slot lanes[i])

@@ -191,6 +191,93 @@ __global__ __launch_bounds__(TB) void k_direct(LeafList L, const uint32_t *__res
     }
 }
 
+// ---- theta = 0 potential (potential.hip's term over the same leaf sequence) -----------------
+// phi_b = -(G * sum over the leaves but b's own of m / sqrt(r2)), the leaves staged and read in
+// k_direct's order, which is the order the potential walk visits them at theta = 0: the same
+// additions from +0.0, bit-identical to the walk.  The own leaf's term m_b / sqrt(soft2) is not
+// zero, so the identity test stays on the fast path too.
+template <bool FAST>
+__device__ __forceinline__ void leaf_potentials(const double4_t &r, const double (&bx)[NB],
+                                                const double (&by)[NB], double soft2,
+                                                const uint32_t (&self)[NB], double (&s)[NB]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const double dx = r.x - bx[b];
+        const double dy = r.y - by[b];
+        const double r2 = dx * dx + dy * dy + soft2;
+        const bool other = (uint32_t)__double_as_longlong(r.w) != self[b];  // BHA:219
+        if (FAST) {
+            // the own leaf adds +0.0 instead of being branched around: s -- a sum from +0.0,
+            // never -0.0 -- is unchanged, and the in-range sequences are finite for every leaf
+            double h;
+            const double rr = sqrt_rn_inrange_h(r2, h);
+            const double invR = rcp_rn_seeded(rr, h + h);
+            s[b] += other ? r.z * invR : 0.0;
+        } else if (other) {
+            s[b] += r.z * (1.0 / sqrt(r2));
+        }
+    }
+}
+
+template <bool FAST>
+__device__ __forceinline__ void sum_tile_potential(const double4_t *s_rec, int cnt,
+                                                   const double (&bx)[NB], const double (&by)[NB],
+                                                   double soft2, const uint32_t (&self)[NB],
+                                                   double (&s)[NB]) {
+    constexpr int U = BH_DIRECT_U;
+    int j = 0;
+    for (; j + U <= cnt; j += U) {
+        double4_t r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u] = s_rec[j + u];  // broadcast reads, issued together
+#pragma unroll
+        for (int u = 0; u < U; ++u) leaf_potentials<FAST>(r[u], bx, by, soft2, self, s);
+    }
+    for (; j < cnt; ++j) leaf_potentials<FAST>(s_rec[j], bx, by, soft2, self, s);
+}
+
+__global__ __launch_bounds__(TB) void k_direct_potential(LeafList L,
+                                                         const uint32_t *__restrict__ d_count,
+                                                         const double *__restrict__ x,
+                                                         const double *__restrict__ y,
+                                                         const uint32_t *__restrict__ cidx,
+                                                         int64_t n, double G, double soft2,
+                                                         double *__restrict__ phi) {
+    __shared__ double4_t s_rec[TILE];
+    int64_t p[NB];
+    bool valid[NB], walks[NB];
+    double bx[NB], by[NB], s[NB];
+    uint32_t self[NB];
+    bool slow = false;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        p[b] = ((int64_t)blockIdx.x * NB + b) * TB + threadIdx.x;
+        valid[b] = p[b] < n;
+        walks[b] = valid[b] && !(cidx[p[b]] & CIDX_DEAD);  // a tombstone gets phi = 0
+        bx[b] = valid[b] ? x[p[b]] : 0.0;
+        by[b] = valid[b] ? y[p[b]] : 0.0;
+        self[b] = valid[b] ? (uint32_t)p[b] : 0xFFFFFFFFu;
+        slow |= walks[b] && !lane_fast_ok(bx[b], by[b], soft2);
+        s[b] = 0.0;
+    }
+    const bool fast = __ballot(slow) == 0ull;
+    const uint32_t nl = *d_count;
+    for (uint32_t t0 = 0; t0 < nl; t0 += TILE) {
+        const int cnt = (int)min((uint32_t)TILE, nl - t0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < cnt; i += TB)
+            s_rec[i] = reinterpret_cast<const double4_t *>(L.rec)[t0 + i];
+        __syncthreads();
+        if (fast)
+            sum_tile_potential<true>(s_rec, cnt, bx, by, soft2, self, s);
+        else
+            sum_tile_potential<false>(s_rec, cnt, bx, by, soft2, self, s);
+    }
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+        if (valid[b]) phi[p[b]] = walks[b] ? -(G * s[b]) : 0.0;
+}
+
 }  // namespace
 
 size_t leaf_select_bytes(int64_t node_cap) {
@@ -229,6 +316,15 @@ void direct_forces(const LeafList &L, const uint32_t *d_count, const double *x, 
     if (hi <= lo) return;
     k_direct<<<(unsigned)((hi - lo + TB * NB - 1) / (TB * NB)), TB, 0, s>>>(L, d_count, x, y, m, lo,
                                                                           hi, G, soft2, a2);
+}
+
+void direct_potential(const LeafList &L, const uint32_t *d_count, const double *x, const double *y,
+                      const uint32_t *cidx, int64_t n, double G, double soft2, double *phi,
+                      hipStream_t s) {
+    if (n <= 0) return;
+    k_direct_potential<<<(unsigned)((n + TB * NB - 1) / (TB * NB)), TB, 0, s>>>(L, d_count, x, y,
+                                                                                cidx, n, G, soft2,
+                                                                                phi);
 }
 
 }  // namespace bh

@@ -215,6 +215,13 @@ struct bh_engine {
     size_t leaf_node_cap = 0;  // node capacity the flags were sized for
     int64_t leaf_cap = 0;
 
+    // potential and global diagnostics (potential.hip), allocated on first use
+    double *phi = nullptr;        // the last bh_compute_potential's phi, slot order
+    int64_t phi_cap = 0;
+    double *diag_part = nullptr;  // the reductions' workgroup partials, then their 8 results
+    hipEvent_t pot_ev[2] = {nullptr, nullptr};  // around the last potential kernel
+    bool pot_timed = false;
+
     bool tree_valid = false;  // lastTree (BHA:304): keys_s / cpl / base / nodes are current
     // Multi-rank engines end a call with a LET build too; lastTree is then built on demand by
     // bh_get_quads from the positions that build saw (lt_x, lt_y), without touching the state
@@ -1483,8 +1490,28 @@ int wave_order_next(bh_engine *e, int slot, int64_t lanes, hipStream_t s) {
     return BH_OK;
 }
 
+// bh_compute_potential's route through evaluate(): the tree exactly as for visits != null (a full
+// build or the carried one, never a LET, not sharded), then the potential of every body into
+// e->phi by slot in place of the forces; a2 is left alone.  run = false: build only (the members
+// of a multi-device handle past the first, whose replicas must take the same jitter).
+struct PotentialEval {
+    bool run;
+};
+
+int potential_bufs(bh_engine *e) {
+    if (e->phi_cap < e->cap || !e->phi) {
+        TRY(dev_alloc(e, e->phi, (size_t)e->cap));
+        e->phi_cap = e->cap;
+    }
+    if (!e->diag_part) TRY(dev_alloc(e, e->diag_part, diag_partial_doubles()));
+    for (hipEvent_t &ev : e->pot_ev)
+        if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return BH_OK;
+}
+
 int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fused = nullptr,
-             bool allow_let = false, bool *let_used = nullptr) {
+             bool allow_let = false, bool *let_used = nullptr,
+             const PotentialEval *pot = nullptr) {
     if (fused) *fused = false;
     if (let_used) *let_used = false;
     // (the pieces are ranges of the slot order: spatially compact only once a full build has
@@ -1532,6 +1559,27 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
     have_forces = have_forces && fp.G == e->fp_ready.G && fp.soft2 == e->fp_ready.soft2 &&
                   fp.theta2 == e->fp_ready.theta2;
     const uint32_t *d_T = e->base + n;
+    if (pot) {  // the potential on this tree, by this engine alone, over the whole list
+        if (!pot->run) return BH_OK;
+        TRY(potential_bufs(e));
+        if (fp.theta2 == 0.0) {  // all pairs over the leaf sequence (direct.hip)
+            TRY(ensure_direct(e));
+            HIPCHK(e, leaf_list_build(e->nodes, d_T, (int64_t)e->node_cap, e->leaf_flags,
+                                      e->leaf_sel, e->leaf_count, e->leaves, n, e->leaf_cover,
+                                      e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
+            HIPCHK(e, hipEventRecord(e->pot_ev[0], e->stream));
+            direct_potential(e->leaves, e->leaf_count, e->st.x, e->st.y, e->st.cidx, n, fp.G,
+                             fp.soft2, e->phi, e->stream);
+        } else {
+            HIPCHK(e, hipEventRecord(e->pot_ev[0], e->stream));
+            potential_walk(e->nodes, e->node_cap, d_T, e->st.x, e->st.y, e->st.cidx, n, e->geo, fp,
+                           e->phi, e->lanes_valid ? e->lanes : nullptr, e->stream);
+        }
+        HIPCHK(e, hipGetLastError());
+        HIPCHK(e, hipEventRecord(e->pot_ev[1], e->stream));
+        e->pot_timed = true;
+        return BH_OK;
+    }
     const bool direct = fp.theta2 == 0.0 && !visits;
     if (direct) {
         TRY(ensure_direct(e));
@@ -3041,9 +3089,11 @@ void bh_destroy(bh_engine *e) {
                     e->m_trav, e->cidx_trav, e->lanes_trav, e->T_trav, e->solo_xchg,
                     e->lt_x, e->lt_y, e->a2_alt, e->lt_keys, e->lt_cpl, e->lt_base, e->mir_stage,
                     e->mir_keep, e->mir_pos, e->mir_tmp, e->mir_idx_stage, e->lanes_next, e->lr_hkey, e->lr_hkey_s,
-                    e->lr_slot, e->lr_scratch};
+                    e->lr_slot, e->lr_scratch, e->phi, e->diag_part};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
+    for (hipEvent_t ev : e->pot_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
     if (e->pin) (void)hipHostFree(e->pin);
@@ -3573,6 +3623,116 @@ static int compute_accelerations_rank(bh_engine *e, double *ax, double *ay, int6
         }
     }
     if (e->profiling) TRY(collect_timings(e));
+    return BH_OK;
+}
+
+// The global sums over the state the caller sees, staged in the caller's list order (as
+// bh_get_bodies stages it) so that the fixed-order reductions depend on the list alone; with_phi:
+// e->phi (slot order, of the build the state is in) enters as sum m phi.
+static int diagnostics_state(bh_engine *e, bool with_phi, bh_diagnostics *out) {
+    *out = bh_diagnostics{};
+    HIPCHK(e, hipSetDevice(e->device));
+    const int64_t n = e->n;
+    out->n = n;
+    if (n <= 0) return BH_OK;
+    TRY(potential_bufs(e));
+    TRY(materialize_positions(e));
+    const BodyState &s = e->view_pending ? e->view : e->st;
+    const double *src[5] = {s.x, s.y, s.vx, s.vy, s.m};
+    double *stage[5] = {e->alt.x, e->alt.y, e->alt.vx, e->alt.vy, e->alt.m};
+    scatter_to_caller(n, s.cidx, 5, src, stage, e->stream);
+    if (with_phi) {
+        const double *ps[1] = {e->phi};
+        double *pd[1] = {e->ax};
+        scatter_to_caller(n, s.cidx, 1, ps, pd, e->stream);
+    }
+    double *res = e->diag_part + diag_partial_doubles() - 8;
+    diag_reduce(n, e->alt.x, e->alt.y, e->alt.vx, e->alt.vy, e->alt.m, with_phi ? e->ax : nullptr,
+                e->diag_part, res, e->stream);
+    HIPCHK(e, hipGetLastError());
+    double h[8];
+    HIPCHK(e, hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+    SYNC(e, e->stream);
+    out->mass = h[0];
+    out->mx = h[1];
+    out->my = h[2];
+    out->px = h[3];
+    out->py = h[4];
+    out->lz = h[5];
+    out->kinetic = h[6];
+    out->potential = with_phi ? 0.5 * h[7] : 0.0;
+    return BH_OK;
+}
+
+// bh_compute_potential / bh_compute_diagnostics(with_potential) on one engine, state semantics of
+// compute_accelerations_rank.  run: this engine evaluates (else it only builds); phi (nullable):
+// caller-order copy-out; diag (nullable): the reductions on the state after the build.
+static int potential_rank(bh_engine *e, double *phi, bool run, bh_diagnostics *diag) {
+    e->prog_api.store(++e->api_calls);
+    HIPCHK(e, hipSetDevice(e->device));
+    const int64_t n = e->n;
+    e->ev_used = 0;
+    e->timings_pending = false;
+    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
+    if (n > 0) {
+        const PotentialEval pe{run};
+        TRY(evaluate(e, nullptr, KICK_NONE, nullptr, false, nullptr, &pe));
+        e->mir_fresh = false;
+        if (run && phi) {
+            const double *ps[1] = {e->phi};
+            double *pd[1] = {e->ax};
+            scatter_to_caller(n, e->st.cidx, 1, ps, pd, e->stream);
+            HIPCHK(e, hipGetLastError());
+        }
+        SYNC(e, e->stream);
+        TRY(check_tree_flags(e));
+        if (run && phi)
+            HIPCHK(e, hipMemcpy(phi, e->ax, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
+    if (diag) TRY(diagnostics_state(e, run && n > 0, diag));
+    if (e->profiling) TRY(collect_timings(e));
+    return BH_OK;
+}
+
+static int potential_call(bh_engine *e, double *phi, bool run, bh_diagnostics *diag) {
+    ASYNC_GUARD(e);
+    COMM_GUARD(e);
+    return fail_multi_rank(e, potential_rank(e, phi, run, diag));
+}
+
+int bh_compute_potential(bh_engine *e, double *phi) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    // (every member builds -- the build may jitter every replica alike; member 0 evaluates and
+    // hands the result out)
+    MULTI_ALL(e, potential_call(m_, r_ == 0 ? phi : nullptr, r_ == 0, nullptr));
+    return potential_call(e, phi, true, nullptr);
+}
+
+int bh_compute_diagnostics(bh_engine *e, int with_potential, bh_diagnostics *out) {
+    if (!e || !out) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (with_potential) {
+        MULTI_ALL(e, potential_call(m_, nullptr, r_ == 0, r_ == 0 ? out : nullptr));
+        return potential_call(e, nullptr, true, out);
+    }
+    if (e->multi) {  // reductions only: member 0's replica (complete at the API boundary)
+        const int rc = bh_compute_diagnostics(MULTI_M0(e), 0, out);
+        if (rc != BH_OK) e->err = bh_last_error(MULTI_M0(e));
+        return rc;
+    }
+    COMM_GUARD(e);
+    return diagnostics_state(e, false, out);
+}
+
+int bh_potential_kernel_ms(const bh_engine *e, double *ms) {
+    if (!e || !ms) return BH_E_INVALID;
+    e = MULTI_M0(e);
+    *ms = 0.0;
+    if (!e->pot_timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, e->pot_ev[0], e->pot_ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *ms = (double)f;
     return BH_OK;
 }
 

@@ -109,6 +109,52 @@ __global__ __launch_bounds__(TB) void k_acc3d(const float4 *__restrict__ pm, uin
     a3[3 * i + 2] = acc.z;
 }
 
+// Centre-of-mass sums (GPU.kt:399-407) in fp64 from the fp32 state: sum x m, y m, z m, m -- each
+// product of two fp32 values is exact in fp64.  Fixed order, no atomics: thread t of workgroup g
+// adds the bodies g * chunk + t, + TB, ... ascending, the threads are combined by a fixed tree in
+// LDS; k_com3d_final adds the workgroups' partials the same way.
+constexpr int COM_MAX_BLOCKS = 1024;
+
+__device__ __forceinline__ void com_tree_sum(double (&v)[4], double (*lds)[TB]) {
+    for (int k = 0; k < 4; ++k) lds[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int w = TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w)
+            for (int k = 0; k < 4; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + w];
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(TB) void k_com3d_partial(const float4 *__restrict__ pm, int64_t n,
+                                                      int64_t chunk, double *__restrict__ part) {
+    __shared__ double lds[4][TB];
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = lo + chunk < n ? lo + chunk : n;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += TB) {
+        const float4 q = pm[i];
+        const double m = (double)q.w;
+        v[0] += (double)q.x * m;
+        v[1] += (double)q.y * m;
+        v[2] += (double)q.z * m;
+        v[3] += m;
+    }
+    com_tree_sum(v, lds);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 4; ++k) part[(size_t)blockIdx.x * 4 + k] = lds[k][0];
+}
+
+__global__ __launch_bounds__(TB) void k_com3d_final(int blocks, const double *__restrict__ part,
+                                                    double *__restrict__ out) {
+    __shared__ double lds[4][TB];
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int g = threadIdx.x; g < blocks; g += TB)
+        for (int k = 0; k < 4; ++k) v[k] += part[(size_t)g * 4 + k];
+    com_tree_sum(v, lds);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 4; ++k) out[k] = lds[k][0];
+}
+
 }  // namespace
 
 struct bh_nbody3d {
@@ -118,6 +164,7 @@ struct bh_nbody3d {
     float4 *pm[2] = {nullptr, nullptr};
     float4 *vel[2] = {nullptr, nullptr};
     float *a3 = nullptr;
+    double *com_part = nullptr;  // centre-of-mass partials (COM_MAX_BLOCKS + 1 groups of 4)
     int cur = 0;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     float last_ms = 0.f;
@@ -179,6 +226,7 @@ void bh_nbody3d_destroy(bh_nbody3d *h) {
         if (h->vel[b]) (void)hipFree(h->vel[b]);
     }
     if (h->a3) (void)hipFree(h->a3);
+    if (h->com_part) (void)hipFree(h->com_part);
     if (h->ev0) (void)hipEventDestroy(h->ev0);
     if (h->ev1) (void)hipEventDestroy(h->ev1);
     if (h->stream) (void)hipStreamDestroy(h->stream);
@@ -276,6 +324,26 @@ int bh_nbody3d_get(const bh_nbody3d *h, float *x, float *y, float *z, float *vx,
         vy[i] = v.y;
         vz[i] = v.z;
     }
+    return BH_OK;
+}
+
+int bh_nbody3d_center_of_mass(bh_nbody3d *h, double out4[4]) {
+    if (!h || !out4) return BH_E_INVALID;
+    for (int k = 0; k < 4; ++k) out4[k] = 0.0;
+    if (h->n == 0) return BH_OK;  // GPU.kt:391
+    HIPCHK3(h, hipSetDevice(h->device));
+    if (!h->com_part)
+        HIPCHK3(h, hipMalloc((void **)&h->com_part, sizeof(double) * 4 * (COM_MAX_BLOCKS + 1)));
+    // whole workgroup strides per chunk, at most COM_MAX_BLOCKS chunks
+    int64_t chunk = (h->n + COM_MAX_BLOCKS - 1) / COM_MAX_BLOCKS;
+    chunk = (chunk + TB - 1) / TB * TB;
+    const int blocks = (int)((h->n + chunk - 1) / chunk);
+    double *res = h->com_part + 4 * COM_MAX_BLOCKS;
+    k_com3d_partial<<<blocks, TB, 0, h->stream>>>(h->pm[h->cur], h->n, chunk, h->com_part);
+    k_com3d_final<<<1, TB, 0, h->stream>>>(blocks, h->com_part, res);
+    HIPCHK3(h, hipGetLastError());
+    HIPCHK3(h, hipMemcpyAsync(out4, res, sizeof(double) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK3(h, hipStreamSynchronize(h->stream));
     return BH_OK;
 }
 

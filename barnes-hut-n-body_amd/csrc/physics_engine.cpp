@@ -204,4 +204,13 @@ BHTree PhysicsEngine::getTreeForDebug() {
     return BHTree(std::move(quads));
 }
 
+bh_diagnostics PhysicsEngine::diagnostics(bool potential) {
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    bh_diagnostics d{};
+    check(bh_compute_diagnostics(eng_, potential ? 1 : 0, &d));
+    if (potential) pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+    return d;
+}
+
 }  // namespace bh

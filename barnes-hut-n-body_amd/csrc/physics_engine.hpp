@@ -72,6 +72,10 @@ public:
     const std::vector<Body> &getBodies() const;       // BHA:335
     void resetBodies(std::vector<Body> &newBodies);   // BHA:342-349
     BHTree getTreeForDebug();                         // BHA:329-332
+    // Conservation read-out of the caller's list (bh_compute_diagnostics; no reference
+    // counterpart).  potential = true builds a tree as step()'s first half does -- its jitter is
+    // written back into the list -- and adds the potential energy; false only reads the state.
+    bh_diagnostics diagnostics(bool potential = true);
 
     double mergeMaxMass = 4000.0;        // BHA:315
     double mergeMinDist = Config::MIN_R; // BHA:321

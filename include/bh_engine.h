@@ -198,7 +198,8 @@ int bh_step(bh_engine *e, int32_t k);
  * Needs the two-buffer mirror (bh_set_mirror(e, 2)), else BH_E_STATE.  Until bh_step_end the
  * caller may only read the mirror it mapped before (bh_map_bodies: the call writes the other
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
- * bh_map_bodies, bh_set_mirror, bh_get_quads and bh_compute_accelerations return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential and
+ * bh_compute_diagnostics return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
  * once its last merge rule is done, before its last traversal; else when the call ends -- and
@@ -246,6 +247,46 @@ int bh_map_bodies(bh_engine *e, const double **x, const double **y, const double
  * of non-empty nodes each body's traversal visited (accumulateForce calls passing the
  * mass == 0 test, BHA:216) — the V of the roofline byte model. */
 int bh_compute_accelerations(bh_engine *e, double *ax, double *ay, int64_t *visits);
+
+/* Per-body gravitational potential of the current state.  State semantics are exactly
+ * bh_compute_accelerations': buildTree() as the first half of step() does it (the jitter's
+ * position mutation included), then the evaluation; a tree-flag error is returned the same way.
+ * Always a full build on this engine, never a locally essential tree, not sharded; on a
+ * multi-device handle every member builds and member 0 evaluates and answers.
+ * phi (length N, caller order; NULL keeps the result on the device): body b visits exactly the
+ * nodes accumulateForce visits for it (BHA:215-239) -- mass-0 nodes skipped, its own leaf skipped
+ * by identity, an internal node taken iff s2 < theta^2 * dist2 (strict) -- and every taken node,
+ * in pre-order, adds
+ *     dx = comX - b.x;  dy = comY - b.y;  r2 = dx*dx + dy*dy + soft2
+ *     s += mass * (1.0 / sqrt(r2))          (IEEE sqrt and divide, no contraction, s from +0.0)
+ * phi_b = -(G * s): bit-reproducible.  An accepted cell that contains b includes b's own mass,
+ * as the force of that cell does (a self term -G m_b / sqrt(r2) that vanishes as theta -> 0); at
+ * theta = 0 nothing is accepted and phi is the exact softened pair potential over the bodies in
+ * the tree (an all-pairs kernel, bit-identical to the walk).  Bodies outside the root cell are
+ * walked (they feel the tree) but are in nobody's sum. */
+int bh_compute_potential(bh_engine *e, double *phi);
+
+/* Conservation read-out, fp64 sums over every live body (out-of-root ones included). */
+typedef struct bh_diagnostics {
+    int64_t n;
+    double mass;          /* sum m                          */
+    double mx, my;        /* sum m*x, sum m*y               */
+    double px, py;        /* sum m*vx, sum m*vy             */
+    double lz;            /* sum m*(x*vy - y*vx)            */
+    double kinetic;       /* sum 0.5*m*(vx*vx + vy*vy)      */
+    double potential;     /* 0.5 * sum m*phi; 0 if not asked */
+} bh_diagnostics;
+/* with_potential = 0: reductions only, over the current state -- no build, no state change.
+ * with_potential = 1: as bh_compute_potential (a build: the state semantics above), then the
+ * reductions on the state after that build; phi stays on the device.
+ * The sums run on the device in the caller's list order, per-workgroup partials in a fixed
+ * order and one final workgroup, without floating-point atomics: two calls on the same state --
+ * or two engines holding the same list -- return identical bits.  N = 0 returns all zeros. */
+int bh_compute_diagnostics(bh_engine *e, int with_potential, bh_diagnostics *out);
+
+/* HIP-event duration (ms) of the last potential kernel launch (bh_compute_potential, or
+ * bh_compute_diagnostics with the potential); 0 before the first. */
+int bh_potential_kernel_ms(const bh_engine *e, double *ms);
 
 /* Indices (into the list as it was before the last bh_step call, ascending) of the bodies the
  * merge rule removed during that call — what a shim needs to apply BHA:519's removeAt to the
@@ -357,6 +398,11 @@ int bh_nbody3d_accelerations(bh_nbody3d *h, float G, float softening, float *ax,
                              float *az);
 int bh_nbody3d_get(const bh_nbody3d *h, float *x, float *y, float *z, float *vx, float *vy,
                    float *vz, float *m, int64_t cap, int64_t *n_out);
+/* GpuNBodyRenderer.computeCenterOfMass() (GPU:390-411) without its read-back of the body buffer:
+ * out4 = sum x*m, sum y*m, sum z*m, sum m over the current bodies, accumulated in fp64 from the
+ * fp32 state by a fixed-order device reduction (no floating-point atomics: the same state gives
+ * the same bits).  The centre of mass is out4[0..2] / out4[3], (0, 0, 0) when out4[3] is 0. */
+int bh_nbody3d_center_of_mass(bh_nbody3d *h, double out4[4]);
 /* device time (ms) of the last bh_nbody3d_step / bh_nbody3d_accelerations call */
 double bh_nbody3d_last_ms(const bh_nbody3d *h);
 
