@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = (
     "bh_create_multi_list", "bh_multi_world", "bh_multi_member", "bh_collective_log",
     "bh_collective_log_clear", "bh_step_begin", "bh_step_positions", "bh_step_end",
     "bh_progress", "bh_compute_potential", "bh_compute_diagnostics", "bh_potential_kernel_ms",
-    "bh_nbody3d_center_of_mass",
+    "bh_nbody3d_center_of_mass", "bh_default_view", "bh_render_bodies", "bh_render_kernel_ms",
 )
 
 
@@ -78,6 +78,18 @@ class BhDiagnostics(ctypes.Structure):
         ("lz", ctypes.c_double),
         ("kinetic", ctypes.c_double),
         ("potential", ctypes.c_double),
+    ]
+
+
+class BhView(ctypes.Structure):
+    """struct bh_view (include/bh_engine.h) -- the view of bh_render_bodies."""
+    _fields_ = [
+        ("view_x", ctypes.c_double),
+        ("view_y", ctypes.c_double),
+        ("zoom", ctypes.c_double),
+        ("width", ctypes.c_int32),
+        ("height", ctypes.c_int32),
+        ("heavy_mass", ctypes.c_double),
     ]
 
 
@@ -179,6 +191,12 @@ def load_library(path: str | None = None):
     lib.bh_compute_potential.argtypes = [_VP, _D]
     lib.bh_compute_diagnostics.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(BhDiagnostics)]
     lib.bh_potential_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_default_view.argtypes = [ctypes.POINTER(BhView)]
+    lib.bh_default_view.restype = None
+    lib.bh_render_bodies.argtypes = [_VP, ctypes.POINTER(BhView), ctypes.POINTER(ctypes.c_uint8),
+                                     ctypes.POINTER(ctypes.c_uint32),
+                                     ctypes.POINTER(ctypes.c_uint32)]
+    lib.bh_render_kernel_ms.argtypes = [_VP, _D]
     lib.bh_get_quads.argtypes = [_VP, _D, _D, _D, ctypes.c_int64, _I64P]
     lib.bh_last_timings.argtypes = [_VP, _D]
     lib.bh_last_tree_nodes.argtypes = [_VP]
@@ -237,6 +255,14 @@ def default_params(**over) -> BhParams:
     for k, v in over.items():
         setattr(p, k, v)
     return p
+
+
+def default_view(**over) -> BhView:
+    v = BhView()
+    load_library().bh_default_view(ctypes.byref(v))
+    for k, val in over.items():
+        setattr(v, k, val)
+    return v
 
 
 SHARD_ROUNDS = 4  # BH_SHARD_ROUNDS (include/bh_engine.h)
@@ -578,6 +604,49 @@ class Engine:
         self._check(self._lib.bh_potential_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
+    def render_bodies(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,
+                      heavy_mass=1000.0, owner=False, counts=False, pixels=True, out=None):
+        """bh_render_bodies: NBodyPanel.paintComponent's body pass (PNL:302-307) over the list
+        get_bodies() would return, rasterised on the device.  Returns `pixels`, uint8 of shape
+        (height, width): 0 nothing, 1 white, 2 black (m >= heavy_mass); with owner= / counts=
+        the tuple (pixels, owner, counts), None for planes not asked for -- owner: uint32, the
+        list index that painted last (0xFFFFFFFF: none), counts: uint32 bodies per pixel.
+        width and height default to the engine's width_px and height_px.  out: a (pixels,
+        owner, counts) tuple of C-contiguous arrays of that shape and dtype to fill instead of
+        new ones (None for a plane not asked for).  Reads the state and changes nothing."""
+        v = BhView(float(view_x), float(view_y), float(zoom),
+                   int(self.params.width_px if width is None else width),
+                   int(self.params.height_px if height is None else height), float(heavy_mass))
+        ok = 1 <= v.width <= 16384 and 1 <= v.height <= 16384  # (else refused below: no planes)
+        shape = (v.height, v.width) if ok else (1, 1)
+        def plane(asked, k, dtype):
+            if not asked:
+                return None
+            a = out[k] if out is not None else None
+            if a is None:
+                return np.empty(shape, dtype=dtype)
+            if a.shape != shape or a.dtype != dtype or not a.flags.c_contiguous:
+                raise ValueError(f"out[{k}] must be a C-contiguous {np.dtype(dtype)} array of "
+                                 f"shape {shape}")
+            return a
+
+        pix = plane(pixels, 0, np.uint8)
+        own = plane(owner, 1, np.uint32)
+        cnt = plane(counts, 2, np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self._lib.bh_render_bodies(
+            self._h, ctypes.byref(v),
+            pix.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if pixels else None,
+            own.ctypes.data_as(u32p) if owner else None,
+            cnt.ctypes.data_as(u32p) if counts else None))
+        return (pix, own, cnt) if (owner or counts or not pixels) else pix
+
+    def render_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last render_bodies' two kernels (bh_render_kernel_ms)."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.bh_render_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def last_removed(self):
         """Indices (list before the last step() call) removed by the merge rule, ascending."""
         need = ctypes.c_int64(0)
@@ -816,6 +885,16 @@ class PhysicsEngine:
         if potential:
             self._pull()
         return d
+
+    def render(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,
+               heavy_mass=1000.0, owner=False, counts=False):
+        """NBodyPanel.paintComponent's body pass over the caller's list (Engine.render_bodies).
+        Nothing is pulled back: the call changes nothing."""
+        self._eng.set_params(self._params())
+        if self._changed():
+            self._push()
+        return self._eng.render_bodies(view_x, view_y, zoom, width, height, heavy_mass,
+                                       owner=owner, counts=counts)
 
     getBodies = get_bodies
     resetBodies = reset_bodies

@@ -581,6 +581,21 @@ size_t diag_partial_doubles();
 void diag_reduce(int64_t n, const double *x, const double *y, const double *vx, const double *vy,
                  const double *m, const double *phi, double *part, double *out8, hipStream_t s);
 
+// ---- launchers (render.hip) ------------------------------------------------------
+// The body pass of a frame (PNL:302-307).  Working planes `packed` and `cnt` (null: no density):
+// render_padded_pixels() uint32 each, zero on entry to render_raster and zero again after
+// render_resolve.  render_raster: slot i of [0, n), unless a tombstone, drawn at
+// toInt((x - view_x) * zoom), toInt((y - view_y) * zoom) if inside the view, as
+// packed[p] = max(packed[p], ((cidx + 1) << 1) | (m >= heavy_mass)) and cnt[p] += 1.
+// render_resolve: pixels (0 / 1 white / 2 black), owner (caller index or 0xFFFFFFFF) and counts,
+// each nullable (counts iff cnt), each of the padded size and 16-byte aligned.
+size_t render_padded_pixels(int32_t width, int32_t height);
+void render_raster(int64_t n, const double *x, const double *y, const double *m,
+                   const uint32_t *cidx, const bh_view &v, uint32_t *packed, uint32_t *cnt,
+                   hipStream_t s);
+void render_resolve(size_t padded_pixels, uint32_t *packed, uint32_t *cnt, uint8_t *pixels,
+                    uint32_t *owner, uint32_t *counts, hipStream_t s);
+
 // ---- launchers (integrate.hip) ---------------------------------------------------
 // a2 indexed by traversal lane when lanes != null (lane i holds body slot lanes[i])
 // lane q's acceleration at a2[2 * gather_slot(gl, q)]

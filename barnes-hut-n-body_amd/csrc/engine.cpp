@@ -38,6 +38,7 @@
 #include "bh_device.hpp"
 #include "bh_engine.h"
 #include "multi.hpp"
+#include "render_view.hpp"
 
 using namespace bh;
 
@@ -221,6 +222,19 @@ struct bh_engine {
     double *diag_part = nullptr;  // the reductions' workgroup partials, then their 8 results
     hipEvent_t pot_ev[2] = {nullptr, nullptr};  // around the last potential kernel
     bool pot_timed = false;
+
+    // bh_render_bodies (render.hip): buffers of its own, allocated on first use, kept while the
+    // padded pixel count is unchanged.  rnd_packed / rnd_cnt are zero between calls (the resolve
+    // kernel re-zeroes what the rasteriser touched); rnd_clean = false: a call failed in between
+    uint32_t *rnd_packed = nullptr, *rnd_cnt = nullptr;
+    uint8_t *rnd_pixels = nullptr;                        // staged planes, device
+    uint32_t *rnd_owner = nullptr, *rnd_counts = nullptr;
+    size_t rnd_pad = 0;  // padded pixels the buffers above are sized for
+    uint8_t *rnd_pin = nullptr;  // pinned host bounce buffer of the staged planes
+    size_t rnd_pin_bytes = 0;
+    bool rnd_clean = false;
+    hipEvent_t rnd_ev[2] = {nullptr, nullptr};  // around the last render's two kernels
+    bool rnd_timed = false;
 
     bool tree_valid = false;  // lastTree (BHA:304): keys_s / cpl / base / nodes are current
     // Multi-rank engines end a call with a LET build too; lastTree is then built on demand by
@@ -3089,14 +3103,18 @@ void bh_destroy(bh_engine *e) {
                     e->m_trav, e->cidx_trav, e->lanes_trav, e->T_trav, e->solo_xchg,
                     e->lt_x, e->lt_y, e->a2_alt, e->lt_keys, e->lt_cpl, e->lt_base, e->mir_stage,
                     e->mir_keep, e->mir_pos, e->mir_tmp, e->mir_idx_stage, e->lanes_next, e->lr_hkey, e->lr_hkey_s,
-                    e->lr_slot, e->lr_scratch, e->phi, e->diag_part};
+                    e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
+                    e->rnd_pixels, e->rnd_owner, e->rnd_counts};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (hipEvent_t ev : e->pot_ev)
         if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->rnd_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
     if (e->pin) (void)hipHostFree(e->pin);
+    if (e->rnd_pin) (void)hipHostFree(e->rnd_pin);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
 }
@@ -3732,6 +3750,132 @@ int bh_potential_kernel_ms(const bh_engine *e, double *ms) {
     if (!e->pot_timed) return BH_OK;
     float f = 0.f;
     if (hipEventElapsedTime(&f, e->pot_ev[0], e->pot_ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *ms = (double)f;
+    return BH_OK;
+}
+
+// The caller-visible state rasterised (render.hip): reads x, y, m, cidx of `view_pending ? view :
+// st` in slot order -- no scatter to caller order, nothing of the state or of what the pipelined
+// engine carries into the next call is written -- into the engine's render buffers.
+static int render_buffers(bh_engine *e, size_t pad, bool pixels, bool owner, bool counts) {
+    if (pad != e->rnd_pad) {  // another view size: made anew
+        void **all[] = {(void **)&e->rnd_packed, (void **)&e->rnd_cnt, (void **)&e->rnd_pixels,
+                        (void **)&e->rnd_owner, (void **)&e->rnd_counts};
+        for (void **q : all) {
+            if (*q) (void)hipFree(*q);
+            *q = nullptr;
+        }
+        e->rnd_pad = pad;
+    }
+    if (!e->rnd_packed) {
+        TRY(dev_alloc(e, e->rnd_packed, pad));
+        HIPCHK(e, hipMemsetAsync(e->rnd_packed, 0, sizeof(uint32_t) * pad, e->stream));
+    }
+    if (counts && !e->rnd_cnt) {
+        TRY(dev_alloc(e, e->rnd_cnt, pad));
+        HIPCHK(e, hipMemsetAsync(e->rnd_cnt, 0, sizeof(uint32_t) * pad, e->stream));
+    }
+    if (pixels && !e->rnd_pixels) TRY(dev_alloc(e, e->rnd_pixels, pad));
+    if (owner && !e->rnd_owner) TRY(dev_alloc(e, e->rnd_owner, pad));
+    if (counts && !e->rnd_counts) TRY(dev_alloc(e, e->rnd_counts, pad));
+    if (!e->rnd_clean) {  // a call that failed between its two kernels left the planes as they were
+        HIPCHK(e, hipMemsetAsync(e->rnd_packed, 0, sizeof(uint32_t) * pad, e->stream));
+        if (e->rnd_cnt)
+            HIPCHK(e, hipMemsetAsync(e->rnd_cnt, 0, sizeof(uint32_t) * pad, e->stream));
+        e->rnd_clean = true;
+    }
+    for (hipEvent_t &ev : e->rnd_ev)
+        if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return BH_OK;
+}
+
+static int render_state(bh_engine *e, const bh_view &v, uint8_t *pixels, uint32_t *owner,
+                        uint32_t *counts) {
+    const size_t npix = (size_t)v.width * (size_t)v.height;
+    const int64_t n = e->n;
+    if (n <= 0) {  // nothing drawn: no device work
+        if (pixels) std::memset(pixels, 0, npix);
+        if (owner) std::memset(owner, 0xFF, sizeof(uint32_t) * npix);
+        if (counts) std::memset(counts, 0, sizeof(uint32_t) * npix);
+        return BH_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    TRY(materialize_positions(e));
+    const size_t pad = render_padded_pixels(v.width, v.height);
+    TRY(render_buffers(e, pad, pixels != nullptr, owner != nullptr, counts != nullptr));
+    const BodyState &s = e->view_pending ? e->view : e->st;  // (not the prebuilt tree's jitter)
+    e->rnd_clean = false;
+    HIPCHK(e, hipEventRecord(e->rnd_ev[0], e->stream));
+    render_raster(n, s.x, s.y, s.m, s.cidx, v, e->rnd_packed, counts ? e->rnd_cnt : nullptr,
+                  e->stream);
+    HIPCHK(e, hipGetLastError());
+    render_resolve(pad, e->rnd_packed, counts ? e->rnd_cnt : nullptr,
+                   pixels ? e->rnd_pixels : nullptr, owner ? e->rnd_owner : nullptr,
+                   counts ? e->rnd_counts : nullptr, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->rnd_ev[1], e->stream));
+    e->rnd_clean = true;
+    e->rnd_timed = true;
+    // BH_RENDER_PINNED=1: through a pinned bounce buffer and a host copy (A/B, read per call)
+    const char *env = std::getenv("BH_RENDER_PINNED");
+    const bool pinned = env && std::atoi(env) != 0;
+    void *dst[3] = {pixels, owner, counts};
+    const void *src[3] = {e->rnd_pixels, e->rnd_owner, e->rnd_counts};
+    const size_t bytes[3] = {npix, sizeof(uint32_t) * npix, sizeof(uint32_t) * npix};
+    if (pinned && e->rnd_pin_bytes < 9 * npix) {
+        if (e->rnd_pin) (void)hipHostFree(e->rnd_pin);
+        e->rnd_pin = nullptr;
+        e->rnd_pin_bytes = 0;
+        HIPCHK(e, hipHostMalloc((void **)&e->rnd_pin, 9 * npix, hipHostMallocDefault));
+        e->rnd_pin_bytes = 9 * npix;
+    }
+    size_t off = 0;
+    for (int k = 0; k < 3; ++k) {
+        if (!dst[k]) continue;
+        HIPCHK(e, hipMemcpyAsync(pinned ? (void *)(e->rnd_pin + off) : dst[k], src[k], bytes[k],
+                                 hipMemcpyDeviceToHost, e->stream));
+        off += bytes[k];
+    }
+    SYNC(e, e->stream);
+    if (pinned) {
+        off = 0;
+        for (int k = 0; k < 3; ++k) {
+            if (!dst[k]) continue;
+            std::memcpy(dst[k], e->rnd_pin + off, bytes[k]);
+            off += bytes[k];
+        }
+    }
+    return BH_OK;
+}
+
+void bh_default_view(bh_view *v) {
+    if (v) view_defaults(v);
+}
+
+int bh_render_bodies(bh_engine *e, const bh_view *v, uint8_t *pixels, uint32_t *owner,
+                     uint32_t *counts) {
+    if (!e || !v) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (const char *why = view_error(*v)) {
+        e->err = why;
+        return BH_E_INVALID;
+    }
+    if (e->multi) {  // every replica is complete at the API boundary: member 0's
+        const int rc = bh_render_bodies(MULTI_M0(e), v, pixels, owner, counts);
+        if (rc != BH_OK) e->err = bh_last_error(MULTI_M0(e));
+        return rc;
+    }
+    COMM_GUARD(e);
+    return render_state(e, *v, pixels, owner, counts);
+}
+
+int bh_render_kernel_ms(const bh_engine *e, double *ms) {
+    if (!e || !ms) return BH_E_INVALID;
+    e = MULTI_M0(e);
+    *ms = 0.0;
+    if (!e->rnd_timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, e->rnd_ev[0], e->rnd_ev[1]) != hipSuccess) return BH_E_DEVICE;
     *ms = (double)f;
     return BH_OK;
 }

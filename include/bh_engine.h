@@ -198,8 +198,8 @@ int bh_step(bh_engine *e, int32_t k);
  * Needs the two-buffer mirror (bh_set_mirror(e, 2)), else BH_E_STATE.  Until bh_step_end the
  * caller may only read the mirror it mapped before (bh_map_bodies: the call writes the other
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
- * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential and
- * bh_compute_diagnostics return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
+ * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
  * once its last merge rule is done, before its last traversal; else when the call ends -- and
@@ -287,6 +287,49 @@ int bh_compute_diagnostics(bh_engine *e, int with_potential, bh_diagnostics *out
 /* HIP-event duration (ms) of the last potential kernel launch (bh_compute_potential, or
  * bh_compute_diagnostics with the potential); 0 before the first. */
 int bh_potential_kernel_ms(const bh_engine *e, double *ms);
+
+/* The body pass of a frame, rasterised on the device: what NBodyPanel.paintComponent's loop over
+ * engine.getBodies() paints (PNL:302-307) -- one pixel per body, black if m >= 1000 (PNL:303),
+ * white otherwise, a later body of the list overwriting an earlier one -- returned as an image
+ * instead of five N-long planes. */
+typedef struct bh_view {
+    double view_x, view_y;   /* NBodyPanel.viewX / viewY (world coords of the screen origin) */
+    double zoom;             /* NBodyPanel.zoom: finite, > 0 */
+    int32_t width, height;   /* panel size in pixels: 1..16384 each, width*height <= 1<<24 */
+    double heavy_mass;       /* PNL:303 colour threshold; bh_default_view sets 1000.0 */
+} bh_view;
+/* view_x = view_y = 0, zoom = 1.0, Config WIDTH_PX x HEIGHT_PX (2400 x 800, CFG:5,8), 1000.0 */
+void bh_default_view(bh_view *v);
+/* pixels, owner, counts: row-major height x width planes; any of them may be NULL.
+ * Exactly PNL:302-307 over the list bh_get_bodies would return.  For body i in caller order
+ *     tx = (x_i - view_x) * zoom;  ty = (y_i - view_y) * zoom             (binary64)
+ *     sx = toInt(tx);  sy = toInt(ty)       (Kotlin's Double.toInt(): NaN gives 0, otherwise
+ *                                            truncation toward zero, saturating at the Int range)
+ * and the body is drawn iff 0 <= sx < width && 0 <= sy < height -- equivalently tx is NaN or
+ * -1 < tx < width, and the same for ty (the test is made in double, before any conversion).
+ * Truncation is not floor: a body up to one pixel left of or above the view lands in column or
+ * row 0, and so does a NaN coordinate, as in the reference.
+ *   owner[p]   the largest caller index drawn on pixel p (the body that painted last);
+ *              0xFFFFFFFF where nothing was drawn
+ *   pixels[p]  0 nothing, 1 white (m[owner] < heavy_mass), 2 black (m[owner] >= heavy_mass)
+ *   counts[p]  the number of bodies drawn on p (the reference has no such plane: the density a
+ *              renderer wants at a million bodies)
+ * Every output is a function of the list alone (integer max and integer add, no floating-point
+ * atomics): two calls, or two engines holding the same list, return identical bytes.
+ * State and errors as bh_compute_diagnostics(e, 0, ...): no build, no jitter, no state change;
+ * the call reads the state the caller sees (never the jittered positions of a tree the pipelined
+ * engine built ahead) and writes only buffers of its own, allocated on first use and kept while
+ * the view size is unchanged.  A multi-device handle answers from member 0's replica, as
+ * bh_get_bodies does.  N = 0: pixels and counts all 0, owner all 0xFFFFFFFF.
+ * BH_E_INVALID (with bh_last_error text): NULL e or v; zoom not finite or <= 0; heavy_mass NaN;
+ * width or height outside 1..16384 or width*height > 1<<24.  BH_E_STATE between bh_step_begin
+ * and bh_step_end. */
+int bh_render_bodies(bh_engine *e, const bh_view *v, uint8_t *pixels, uint32_t *owner,
+                     uint32_t *counts);
+
+/* HIP-event duration (ms) of the last bh_render_bodies' two kernels (rasterise + resolve); 0
+ * before the first (a call with N = 0 launches nothing and leaves it as it was). */
+int bh_render_kernel_ms(const bh_engine *e, double *ms);
 
 /* Indices (into the list as it was before the last bh_step call, ascending) of the bodies the
  * merge rule removed during that call — what a shim needs to apply BHA:519's removeAt to the
