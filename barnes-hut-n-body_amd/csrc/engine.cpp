@@ -844,6 +844,12 @@ int collect_timings(bh_engine *e) {
 #ifndef BH_LANE_DEFER
 #define BH_LANE_DEFER 1  // pipelined steps re-sort beside the first traversal (lane_refresh_beside)
 #endif
+// "theta is zero" is a statement about theta^2, the value the criterion uses (BHA:226-228) and
+// the one evaluate() picks the all-pairs kernel by: for 0 < |theta| < ~1.5e-162 the square
+// underflows to zero.  Everything that prepares for a tree walk (lane maps, pipelining, LET
+// builds, the snapshot) asks this, so that it never disagrees with the kernel choice.
+bool theta2_is_zero(const bh_engine *e) { return e->p.theta * e->p.theta == 0.0; }
+
 // overlap: the pipelined step's build on stream `s` -- into nodes_alt and alt without the
 // velocities (permute_velocities follows) and without the final swap (the caller swaps)
 // overlap: the pipelined step's next tree, built beside the second traversal into nodes_alt /
@@ -879,7 +885,7 @@ int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, b
     if (keep_v) tb.src.vx = tb.src.vy = nullptr;
     // Hilbert waves (every rank alike): re-sorted every BH_LANE_REFRESH builds, carried through
     // the build's permutation by k_emit_com in between
-    const bool use_lanes = BH_LANE_REFRESH > 0 && n > 0 && e->p.theta != 0.0;
+    const bool use_lanes = BH_LANE_REFRESH > 0 && n > 0 && !theta2_is_zero(e);
     const int every = (e->comm || e->group || e->solo) ? BH_LANE_REFRESH_SHARDED : BH_LANE_REFRESH;
     const bool due = use_lanes && e->lanes_valid && e->lanes_age >= every;
     // (pipelined steps: the re-sort is left to the next first traversal's side, see
@@ -919,7 +925,7 @@ int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, b
     e->st_morton = true;
     if (overlap) return BH_OK;
     if (n > 0) std::swap(e->st, e->alt);
-    if (e->solo && n > 0 && e->p.theta != 0.0) {  // the peers' cell values for later LET builds
+    if (e->solo && n > 0 && !theta2_is_zero(e)) {  // the peers' cell values for later LET builds
         if (!e->solo_table) {
             TRY(dev_alloc(e, e->solo_table, LET_TSTRIDE));
             HIPCHK(e, hipMemsetAsync(e->solo_table, 0, sizeof(LetCell) * LET_TSTRIDE, e->stream));
@@ -1531,7 +1537,7 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
     // (the pieces are ranges of the slot order: spatially compact only once a full build has
     // put the state into Morton order -- after a reset it is the caller's order)
     if (allow_let && !visits && (e->comm || e->group || e->solo) && let_active(e) &&
-        e->p.theta != 0.0 &&
+        !theta2_is_zero(e) &&
         e->st_morton && e->let_age < BH_LET_REFRESH) {
         bool done = false;
         TRY(evaluate_let(e, kick, &done));
@@ -1556,7 +1562,7 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
         TRY(sync_velocities(e));        // before the full build permutes the state
         TRY(mark(e, -1));
         TRY(build(e));
-        if ((e->comm || e->group || e->solo) && let_active(e) && e->p.theta != 0.0 && n > 0) {
+        if ((e->comm || e->group || e->solo) && let_active(e) && !theta2_is_zero(e) && n > 0) {
             // the LET selections until the next full build scan only the slot blocks whose box
             // (the cells of their bodies now, in this build's slot order) may reach a built cell
             TRY(let_alloc(e, 0));
@@ -1849,7 +1855,7 @@ int finish_merges(bh_engine *e, uint32_t *overflow, uint32_t *tree_flags = nullp
     }
     e->n = n - (int64_t)nd;
     e->inv_valid = false;  // another n: another exchange layout
-    if ((e->comm || e->group || e->solo) && let_active(e) && e->p.theta != 0.0 && e->n > 0 &&
+    if ((e->comm || e->group || e->solo) && let_active(e) && !theta2_is_zero(e) && e->n > 0 &&
         e->st_morton && !e->pos_pending) {
         // the LET selections until the next full build: boxes of the compacted slots from the
         // positions now (materialized at the call's end), the displacement bound restarting here
@@ -2013,7 +2019,7 @@ int64_t deep_pipe_max_n() {
 #endif
 bool pipelined(const bh_engine *e, bool last) {
     return BH_PIPELINE && BH_FUSE_KICK && (!last || BH_PIPE_LAST) && e->n > 0 && !e->comm &&
-           !e->group && !e->solo && e->p.theta != 0.0;
+           !e->group && !e->solo && !theta2_is_zero(e);
 }
 
 // The overlap and mirror streams of a one-GPU engine.  HIP hands a process's streams its few
@@ -3276,7 +3282,7 @@ static int step_call_rank(bh_engine *e, int32_t k) {
     const bool may_merge = k > 0 && e->n > 1 && e->p.merge_min_dist > 0.0 && e->heavy_possible;
     // a multi-rank call with LET builds may have to be replayed with a larger subset capacity
     const bool may_let = k > 0 && e->n > 0 && (e->comm || e->group || e->solo) && let_active(e) &&
-                         e->p.theta != 0.0;
+                         !theta2_is_zero(e);
     if (may_merge || may_let) TRY(snapshot(e));
     // the previous call's pipelined last step built this call's first tree (a replay does not
     // use it: restore() starts from the caller-visible state)

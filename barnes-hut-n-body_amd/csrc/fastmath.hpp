@@ -47,6 +47,11 @@ __device__ __forceinline__ double sqrt_rn_inrange_h(double x, double &hout) {
 // two steps -- and the final residual correction is that sequence's last two operations.
 // The seeds: 2h for 1/sqrt(d2) (from the sqrt above), invR*invR for 1/d2 (rel. err 2^-51).
 // bh_selftest_fast_math checks these against the IEEE operations on random operands.
+// KNOWN GAP: for a divisor whose significand is all ones (b = 2^k (2 - 2^-52)) the residual
+// step is correctly rounded only from a y that already is RN(1/b), and the Newton step from a
+// 2^-44 seed lands below the midpoint: the result is 2^-k-1 instead of 2^-k-1 (1 + 2^-52).
+// Random operands never meet it (2^-52 per term).  A body far outside the root can meet it at
+// many nodes at once; lane_fast_ok's position bound (below) keeps such bodies off this path.
 __device__ __forceinline__ double rcp_rn_seeded(double b, double y0) {
     const double e = __builtin_fma(-b, y0, 1.0);
     const double y = __builtin_fma(y0, e, y0);
@@ -67,9 +72,17 @@ __device__ __forceinline__ double rcp_rn_inrange(double b) {
 // Wave-uniform precondition for the exact fast paths: every tree node's centre of mass lies
 // within the root cell or 2e-3 of it (a convex combination of inserted bodies; a jittered
 // leaf body moved by at most 2 x 1e-3), so |comX|, |comY| < 2^31 always.  If the lane's own
-// body is finite with |x|, |y| < 2^250 and soft2 is in [2^-600, 2^500], every dist2 of the
-// traversal is in [soft2, 2^503] and both sqrt and the reciprocals stay in the range where
+// body is finite with |x|, |y| < 2^32 and soft2 is in [2^-600, 2^500], every dist2 of the
+// traversal is in [soft2, 2^67] and both sqrt and the reciprocals stay in the range where
 // sqrt_rn_inrange / rcp_rn_inrange equal the full IEEE sequences.
+// Why 2^32 and not the range's own 2^250: dx = RN(comX - x) is -x exactly whenever |comX| is
+// below half an ulp of x, and then (the other axis and soft2 vanishing against x^2 likewise)
+// d2 = RN(x^2) and r = RN(sqrt(d2)) = |x|: the divisor of rcp_rn_seeded copies the body's own
+// significand, and a coordinate with an all-ones significand -- nextafter(2^k, 0) -- meets the
+// known gap above at every such node.  From |x| ~ 2^53 that is every node within 0.5 of the
+// axis' zero, from 2^64 most of a screen.  Below 2^32 it takes a node within 2^-22 of the zero:
+// a coincidence of the order of the gap's own, not a property of the body.  A body beyond the
+// bound walks the IEEE path.
 // Self term.  In the fast path a body's own leaf is not excluded: its dx = dy = +0.0 exactly
 // (the leaf holds the body's own position), so the term is f * (+-0) * invR = +-0 with f and
 // invR finite, and adding +-0 leaves the running sum unchanged (the sum starts at +0.0 and can
@@ -87,7 +100,7 @@ __device__ __forceinline__ bool fast_s2_ok(double s2root) {
 }
 
 __device__ __forceinline__ bool lane_fast_ok(double bx, double by, double soft2) {
-    return __builtin_fabs(bx) < 0x1p250 && __builtin_fabs(by) < 0x1p250 && soft2 >= 0x1p-600 &&
+    return __builtin_fabs(bx) < 0x1p32 && __builtin_fabs(by) < 0x1p32 && soft2 >= 0x1p-600 &&
            soft2 <= 0x1p500;
 }
 

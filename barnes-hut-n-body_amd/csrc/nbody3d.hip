@@ -44,32 +44,41 @@ __device__ __forceinline__ void accumulate(const float4 *__restrict__ pm, uint32
         const uint32_t cnt = min((uint32_t)TILE, n - t0);
         __syncthreads();
         for (uint32_t i = threadIdx.x; i < TILE; i += TB) {
-            const float4 q = i < cnt ? pm[t0 + i] : make_float4(0.f, 0.f, 0.f, 0.f);  // m = 0 pads
+            const float4 q = i < cnt ? pm[t0 + i] : make_float4(0.f, 0.f, 0.f, 0.f);
             tile.x[i] = q.x;
             tile.y[i] = q.y;
             tile.z[i] = q.z;
             tile.m[i] = q.w;
         }
         __syncthreads();
-        // self: its mass enters as 0, so its term is exactly 0 (soft2 > 0 keeps r2 > 0)
+        // An excluded slot -- self (GPU.kt:134), or the pad beside the last body of an odd tile --
+        // has its weight s replaced by +0, so its terms are s * d = +-0 with d finite whatever
+        // r2 is: with softening 0 self has r2 = 0, rsq = inf, and a body at the pad's (0, 0, 0)
+        // likewise, and masking the mass alone would add 0 * inf = NaN.  Adding +-0 leaves a
+        // nonzero sum unchanged and a +0 sum +0; only a sum that is -0 (a negative term that
+        // underflowed past the smallest denormal) can turn +0 by it.
         const uint32_t sl = self - t0;
-#pragma unroll 4
-        for (uint32_t j = 0; j < TILE; j += 2) {
+        auto pair = [&](uint32_t j, bool pad) __attribute__((always_inline)) {
             const float2_t dx = *reinterpret_cast<const float2_t *>(tile.x + j) - px;
             const float2_t dy = *reinterpret_cast<const float2_t *>(tile.y + j) - py;
             const float2_t dz = *reinterpret_cast<const float2_t *>(tile.z + j) - pz;
-            float2_t m = *reinterpret_cast<const float2_t *>(tile.m + j);
-            if (j == (sl & ~1u)) m = (sl & 1u) ? float2_t{m.x, 0.f} : float2_t{0.f, m.y};
+            const float2_t m = *reinterpret_cast<const float2_t *>(tile.m + j);
             const float2_t r2 = pk_fma(dz, dz, pk_fma(dy, dy, pk_fma(dx, dx, s2)));
             float2_t inv;
             inv.x = __builtin_amdgcn_rsqf(r2.x);
             inv.y = __builtin_amdgcn_rsqf(r2.y);
             const float2_t inv3 = inv * inv * inv;
-            const float2_t s = (g2 * m) * inv3;  // (uG * other.w) * d * invR3
+            float2_t s = (g2 * m) * inv3;  // (uG * other.w) * d * invR3
+            if (j == (sl & ~1u)) s = (sl & 1u) ? float2_t{s.x, 0.f} : float2_t{0.f, s.y};
+            if (pad) s.y = 0.f;
             ax = pk_fma(s, dx, ax);
             ay = pk_fma(s, dy, ay);
             az = pk_fma(s, dz, az);
-        }
+        };
+        const uint32_t whole = cnt & ~1u;  // the pairs of two bodies; the pads past them add nothing
+#pragma unroll 4
+        for (uint32_t j = 0; j < whole; j += 2) pair(j, false);
+        if (cnt & 1u) pair(whole, true);
     }
     acc = make_float3(ax.x + ax.y, ay.x + ay.y, az.x + az.y);
 }

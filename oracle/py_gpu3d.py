@@ -38,6 +38,32 @@ def accelerations(x, y, z, m, G=80.0, softening=1.0, block=2048):
     return ax, ay, az
 
 
+def accelerations_and_term_sums(x, y, z, m, G=80.0, softening=1.0):
+    """accelerations() and, per body and component, sum_j |t_ij| of the terms t_ij it adds
+    (t = w * d): the scale of a summation error bound.  The accelerations are the same
+    expressions summed the same way, hence the same bits."""
+    x, y, z, m = (np.asarray(a, dtype=np.float64) for a in (x, y, z, m))
+    n = len(x)
+    soft2 = float(softening) * float(softening)
+    acc = [np.zeros(n), np.zeros(n), np.zeros(n)]
+    mag = [np.zeros(n), np.zeros(n), np.zeros(n)]
+    block = 2048
+    for i0 in range(0, n, block):
+        i1 = min(n, i0 + block)
+        d = [c[None, :] - c[i0:i1, None] for c in (x, y, z)]
+        r2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + soft2
+        with np.errstate(divide="ignore", invalid="ignore"):
+            inv = 1.0 / np.sqrt(r2)
+            w = (G * m[None, :]) * inv * inv * inv
+        idx = np.arange(i0, i1)
+        w[idx - i0, idx] = 0.0
+        for k in range(3):
+            t = w * d[k]
+            acc[k][i0:i1] = t.sum(axis=1)
+            mag[k][i0:i1] = np.abs(t).sum(axis=1)
+    return tuple(acc), tuple(mag)
+
+
 def step(x, y, z, vx, vy, vz, m, k=1, dt=0.005, G=80.0, softening=1.0):
     x, y, z, vx, vy, vz, m = (np.array(a, dtype=np.float64) for a in (x, y, z, vx, vy, vz, m))
     for _ in range(k):

@@ -162,6 +162,122 @@ def _negative_cells():
     return x, y, vx, vy, m
 
 
+# ---- the edges of the parameter space (shared with tests/test_gpu_fallback.py) ---------------
+# The engine's force and potential kernels take their exact reduced-range sequences only while
+# soft2 is in [2^-600, 2^500], |x|, |y| < 2^32 and |G m^2| < 2^400 (csrc/fastmath.hpp); outside
+# they run full IEEE sqrt / divide.  These values sit on and beyond those guards, so the C
+# restatement is pinned here by the independent Python one before the GPU is compared with it.
+P600, P500, P250 = 2.0 ** -600, 2.0 ** 500, 2.0 ** 250
+SOFT2_EDGES = [0.0, float(np.nextafter(P600, 0.0)), P600, P500, float(np.nextafter(P500, np.inf)),
+               float("inf")]
+FAR_BODIES = [("x", 1e100), ("x", -P250), ("x", float(np.nextafter(P250, 0.0))), ("y", 1e200),
+              ("y", -1e160)]
+HEAVY_MASSES = [1e59, 1e61, -1e70, 1e100]  # G m^2 < 2^400 holds for the first only
+G_EDGES = [0.0, -80.0, 1e200]
+THETA_EDGES = [-0.5, -0.0, 1e-200, 1e-160, 1e160, float("inf")]  # theta^2: 0 from 1e-200
+DT_EDGES = [0.0, -0.005]
+
+
+def coincident_pair(arrs, i, j):
+    """`arrs` with body j moved onto body i (the build's jitter separates or drops them)."""
+    x, y, vx, vy, m = (a.copy() for a in arrs)
+    x[j], y[j] = x[i], y[i]
+    return x, y, vx, vy, m
+
+
+def with_far_bodies(arrs):
+    """`arrs` plus the five FAR_BODIES (m = 1.5, at rest, the other coordinate on the screen)
+    at list indices 0, ~n/4, ~n/2, ~3n/4 and last.  They lie outside the root cell: never
+    inserted (BHA:126), but walked, kicked and drifted."""
+    out = [a.copy() for a in arrs]
+    n = len(out[0])
+    at = [0, n // 4, n // 2, 3 * n // 4, n]
+    done = 0
+    for k, ((axis, v), i) in enumerate(zip(FAR_BODIES, at)):
+        on_screen = 300.0 + 50.0 * k
+        row = (v, on_screen) if axis == "x" else (on_screen + 700.0, v)
+        # (+ done: the earlier insertions shifted the list)
+        out = [np.insert(a, i + done, val) for a, val in zip(out, (*row, 0.0, 0.0, 1.5))]
+        done += 1
+    return tuple(out)
+
+
+def with_guard_bodies(arrs):
+    """`arrs` plus six bodies around |x|, |y| = 2^32, the position bound of the engine's fast
+    path.  Beyond it: x = -2^32, y = 2^32 and x = nextafter(2^64, 0).  Inside: x = 3 * 2^30,
+    x = nextafter(2^32, 0) and y = -nextafter(2^32, 0).  The nextafter values have a
+    significand of all ones, the one the fast path's reciprocal depends on."""
+    ones32, ones64 = float(np.nextafter(2.0 ** 32, 0.0)), float(np.nextafter(2.0 ** 64, 0.0))
+    rows = [(-2.0 ** 32, 350.0), (ones32, 450.0), (1000.0, 2.0 ** 32), (1100.0, -ones32),
+            (ones64, 500.0), (3.0 * 2.0 ** 30, 520.0)]
+    out = [a.copy() for a in arrs]
+    n = len(out[0])
+    at = (n // 6, n // 3, n // 2, 2 * n // 3, 5 * n // 6, n)
+    for k, (row, i) in enumerate(zip(rows, at)):
+        out = [np.insert(a, i + k, val) for a, val in zip(out, (*row, 0.0, 0.0, 1.5))]
+    return tuple(out)
+
+
+def with_heavy_body(arrs, mass, index):
+    x, y, vx, vy, m = (a.copy() for a in arrs)
+    m[index] = mass
+    return x, y, vx, vy, m
+
+
+def massless_cells_scene(n=3000):
+    """A uniform cloud in which every body of a few boxes has negative mass, so the cells
+    inside them have mass 0 (BHA:189-192) and are never entered (BHA:216) -- with two
+    observers that would sit at distance 0 from such a cell if a walk did not return there
+    but took the cell's record as a node: a body at exactly (0, 0) and a negative-mass body at
+    the exact centre of the depth-6 cell (40, 30) of the 2400 x 800 root, which is one of the
+    massless cells.  With soft2 = 0 such a visit is 0 * (1 / 0)."""
+    x, y, vx, vy, m = (a.copy() for a in scenes.uniform(n, 0.5, seed=9))
+    for cx, cy, half in ((600.0, 300.0, 160.0), (1800.0, 500.0, 90.0), (1200.0, 100.0, 40.0)):
+        inside = (np.abs(x - cx) < half) & (np.abs(y - cy) < half)
+        m[inside] = -0.3
+    w = 2.0 * 1202.0 / 64.0  # depth-6 cells of the root [-2, 2402) x [-802, 1602)
+    x0, y0 = -2.0 + 40 * w, -802.0 + 30 * w
+    inside = (x >= x0) & (x < x0 + w) & (y >= y0) & (y < y0 + w)
+    m[inside] = -0.3
+    ex = [0.0, x0 + 0.5 * w, x0 + 3.0, x0 + w - 4.0, x0 + 11.0]
+    ey = [0.0, y0 + 0.5 * w, y0 + 5.0, y0 + 7.0, y0 + w - 2.0]
+    em = [1.0, -0.3, -0.3, -0.3, -0.3]
+    z = np.zeros(5)
+    return tuple(np.concatenate([a, b]) for a, b in zip((x, y, vx, vy, m), (ex, ey, z, z, em)))
+
+
+def _edge_disk():
+    """A disk of 300 bodies around a 5e4 central mass, with one coincident pair."""
+    return coincident_pair(scenes.galaxy_disk(300, seed=5, r=300.0), 100, 200)
+
+
+def _edge_cases():
+    disk = _edge_disk
+    out = []
+    for s2 in SOFT2_EDGES:
+        for theta in (0.5, 0.0):
+            out.append((f"soft2_{s2!r}_theta{theta}", disk, dict(soft2=s2, theta=theta)))
+    for theta in (0.5, 0.0):
+        out.append((f"far_theta{theta}", lambda: with_far_bodies(_edge_disk()), dict(theta=theta)))
+    for theta in (0.5, 0.0):
+        out.append((f"guard32_theta{theta}", lambda: with_guard_bodies(_edge_disk()),
+                    dict(theta=theta)))
+    for hm in HEAVY_MASSES:
+        for tag, over in (("walk_nomerge", dict(theta=0.5, merge_min_dist=0.0)),
+                          ("walk_merge", dict(theta=0.5)),
+                          ("direct_nomerge", dict(theta=0.0, merge_min_dist=0.0))):
+            out.append((f"heavy_{hm!r}_{tag}",
+                        lambda hm=hm: with_heavy_body(_edge_disk(), hm, 150), over))
+    out.append(("massless_cells_soft2_0", lambda: massless_cells_scene(300), dict(soft2=0.0)))
+    out += [(f"G_{g!r}", disk, dict(G=g)) for g in G_EDGES]
+    out += [(f"theta_{t!r}", disk, dict(theta=t)) for t in THETA_EDGES]
+    out += [(f"dt_{d!r}", disk, dict(dt=d)) for d in DT_EDGES]
+    return [(name, make, over, 2) for name, make, over in out]
+
+
+EDGE = _edge_cases()
+
+
 @pytest.mark.parametrize("name,make,over,k", CROSS, ids=[c[0] for c in CROSS])
 def test_c_and_python_restatements_agree(name, make, over, k):
     ref, pe = _both(make(), **over)
@@ -169,6 +285,32 @@ def test_c_and_python_restatements_agree(name, make, over, k):
         ref.step(1)
         pe.step()
     _assert_same(ref, pe)
+
+
+@pytest.mark.parametrize("name,make,over,k", EDGE, ids=[c[0] for c in EDGE])
+def test_c_and_python_restatements_agree_at_the_edges(name, make, over, k):
+    """Bit for bit as above, on parameters and bodies at and beyond the guards of the engine's
+    fast paths, and every word of the result finite (an all-NaN state would agree with itself)."""
+    ref, pe = _both(make(), **over)
+    for _ in range(k):
+        ref.step(1)
+        pe.step()
+    _assert_same(ref, pe)
+    for f, a in zip(FIELDS, ref.get_bodies()):
+        assert np.all(np.isfinite(a)), f"{f} is not finite"
+
+
+def test_far_body_helper_places_them_where_it_says():
+    arrs = with_far_bodies(_edge_disk())
+    n = len(arrs[0])
+    assert n == 305 and arrs[0][0] == 1e100 and arrs[1][n - 1] == -1e160
+    far = (np.abs(arrs[0]) > 1e50) | (np.abs(arrs[1]) > 1e50)
+    assert far.sum() == 5
+    got = sorted(arrs[0][far].tolist() + arrs[1][far].tolist())
+    assert [v for v in got if abs(v) > 1e50] == sorted(v for _, v in FAR_BODIES)
+    base = _edge_disk()
+    for a, b in zip(arrs, base):  # the other bodies keep their order
+        assert bits_equal(a[~far], b)
 
 
 def test_restatements_agree_on_visits_and_quads():

@@ -17,6 +17,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 
 import bh_amd
 from bh_amd import scenes
@@ -154,6 +155,27 @@ def test_theta0_walk_equals_the_vectorised_form():
     cfg = make_cfg(theta=0.0)
     walk, st_w = checker_phi(arrs, cfg)
     vec, st_v = theta0_phi(arrs, cfg)
+    assert bits_equal(walk, vec)
+    for a, b in zip(st_w, st_v):
+        assert bits_equal(a, b)
+
+
+@pytest.mark.parametrize("case", ["soft2_0", "far"])
+def test_theta0_walk_equals_the_vectorised_form_at_the_edges(case):
+    """The two checkers against each other where the engine leaves its fast path: soft2 = 0
+    (the own leaf's 1 / sqrt(0) must be skipped, not multiplied away) and bodies far outside
+    the root cell (dx * dx overflows: 1 / sqrt(inf) = 0).  Every phi is finite."""
+    from test_oracle import with_far_bodies
+    arrs = scenes.two_disks(300, 100)
+    cfg = make_cfg(theta=0.0)
+    if case == "soft2_0":
+        cfg["soft2"] = 0.0
+    else:
+        arrs = with_far_bodies(arrs)
+    with np.errstate(over="ignore", divide="ignore"):
+        walk, st_w = checker_phi(arrs, cfg)
+        vec, st_v = theta0_phi(arrs, cfg)
+    assert np.all(np.isfinite(walk))
     assert bits_equal(walk, vec)
     for a, b in zip(st_w, st_v):
         assert bits_equal(a, b)
