@@ -295,6 +295,7 @@ struct TreeBuffers {
     uint32_t *cnt, *base;  // node slots per sorted body; exclusive scan (n + 1 entries)
     uint32_t *cell_start;  // [4^D0 + 1] first sorted body of each depth-D0 cell
     uint32_t *lanes_remap = nullptr;  // traversal lane map to carry through this build (or null)
+    bool lane_sort = false;           // lane_order re-sorts with the radix sort (BH_LANE_ORDER_SORT)
     Node *nodes;
     uint32_t *scalars;     // [1] = error flags
     uint32_t *span_list;   // [(J + 1) * span_stride]: chunk-spanning node per (level, boundary)
@@ -333,10 +334,14 @@ void permute_velocities(int64_t n, const uint32_t *perm, const double *svx, cons
 hipError_t lane_order(const TreeBuffers &b, int64_t n, int J, bool refresh, uint32_t *lanes,
                       hipStream_t s);
 // The refresh half of lane_order on its own buffers (the pipelined step runs it beside the next
-// first traversal, engine.cpp): Hilbert keys of the sorted Morton keys, radix-sorted with slots.
+// first traversal, engine.cpp): lanes = the slots 0..n-1 stably sorted by the Hilbert key of
+// their sorted Morton keys.  The slots of one key are already one run in their final order, so
+// the runs are scattered whole (counts and scans: hkey and scratch only); sort: the radix sort
+// of (key, slot) pairs instead (hkey_s and slot too), same result.  scratch: lane_sort_bytes(n)
+// serves either.
 hipError_t lane_order_into(const uint64_t *keys_s, int64_t n, int J, uint32_t *hkey,
                            uint32_t *hkey_s, uint32_t *slot, void *scratch, size_t scratch_bytes,
-                           uint32_t *lanes, hipStream_t s);
+                           uint32_t *lanes, hipStream_t s, bool sort);
 size_t lane_sort_bytes(int64_t n);
 
 // ---- launchers (traverse.hip) ----------------------------------------------------

@@ -247,6 +247,7 @@ struct bh_engine {
     uint32_t *lanes = nullptr;
     bool lanes_valid = false;  // the map is a permutation of the current slots
     int lanes_age = 0;         // builds since the last Hilbert sort
+    bool lane_sort = false;    // BH_LANE_ORDER_SORT=1 at creation: re-sort with the radix sort
     // a due re-sort of the pipelined step's lane map, run beside the next first traversal on its
     // own buffers (lane_refresh_beside) and swapped in before the second build
     bool lane_defer = false;   // this overlapped build may leave a due re-sort to that
@@ -772,6 +773,7 @@ TreeBuffers tree_buffers(bh_engine *e) {
     b.spl_nb = e->spl_nb;
     b.bcount = e->bcount;
     b.bstart = e->bstart;
+    b.lane_sort = e->lane_sort;
     return b;
 }
 
@@ -835,8 +837,12 @@ int collect_timings(bh_engine *e) {
 #ifndef BH_LANE_REFRESH
 // builds between Hilbert re-sorts of the lane map (0: Morton lanes).  With the re-sort beside the
 // first traversal (BH_LANE_DEFER) a fresher map pays: C3 1.84-1.85 ms per step at 16, 1.82-1.83 at
-// 8, 1.814-1.820 at 6, 1.82-1.83 at 4 (round 4, profiles/r04L2_lane_refresh_ab.txt)
-#define BH_LANE_REFRESH 6
+// 8, 1.814-1.820 at 6, 1.82-1.83 at 4 (round 4, profiles/r04L2_lane_refresh_ab.txt) -- with the
+// radix sort, ~0.76 ms of kernels per re-sort.  The run scatter (tree_build.hip lane_order_into)
+// takes ~0.06 ms beside the traversal: means of 6 interleaved runs 1.7122 at 6, 1.7079 at 3,
+// 1.7081 at 2, 1.7129 at 1, the sort at 6 1.7151 (profiles/r07_lane_scatter_ab.md: all within
+// each other's spread)
+#define BH_LANE_REFRESH 3
 #endif
 #ifndef BH_LANE_REFRESH_SHARDED
 #define BH_LANE_REFRESH_SHARDED 16  // multi-rank engines (no pipelined step: the re-sort is in line)
@@ -2390,7 +2396,7 @@ int snapshot_positions(bh_engine *e) {
     return BH_OK;
 }
 
-// The lane map's due Hilbert re-sort (build_into), from the prebuilt tree's sorted keys, on the
+// The lane map's due Hilbert re-order (build_into), from the prebuilt tree's sorted keys, on the
 // overlap stream beside the first traversal -- which walks the map carried through that build --
 // into lanes_next, swapped in before the second build carries it on (evaluate_pipelined).  The
 // traversal writes none of these buffers (its fused epilogue writes keys / keys32, not keys_s).
@@ -2408,15 +2414,17 @@ int lane_refresh_beside(bh_engine *e) {
         if (e->lr_scratch) (void)hipFree(e->lr_scratch);
         e->lr_scratch = nullptr;
         e->lr_cap = 0;
-        for (uint32_t **q : {&e->lanes_next, &e->lr_hkey, &e->lr_hkey_s, &e->lr_slot})
-            TRY(dev_alloc(e, *q, (size_t)e->cap));
+        for (uint32_t **q : {&e->lanes_next, &e->lr_hkey}) TRY(dev_alloc(e, *q, (size_t)e->cap));
+        if (e->lane_sort)  // (the radix sort's second key buffer and its slot values)
+            for (uint32_t **q : {&e->lr_hkey_s, &e->lr_slot}) TRY(dev_alloc(e, *q, (size_t)e->cap));
         e->lr_scratch_bytes = lane_sort_bytes(e->cap);
         HIPCHK(e, hipMalloc(&e->lr_scratch, e->lr_scratch_bytes));
         e->lr_cap = e->cap;
     }
     if (!e->lr_ev) HIPCHK(e, hipEventCreateWithFlags(&e->lr_ev, kPipeEvFlags));
     HIPCHK(e, lane_order_into(e->keys_s, n, e->geo.J, e->lr_hkey, e->lr_hkey_s, e->lr_slot,
-                              e->lr_scratch, e->lr_scratch_bytes, e->lanes_next, e->pipe_stream));
+                              e->lr_scratch, e->lr_scratch_bytes, e->lanes_next, e->pipe_stream,
+                              e->lane_sort));
     HIPCHK(e, hipEventRecord(e->lr_ev, e->pipe_stream));
     e->lr_ready = true;
     return BH_OK;
@@ -2569,6 +2577,7 @@ int engine_init(bh_engine *e, const bh_params *p, int device) {
         e->let_on = std::strcmp(v, "0") != 0;
         e->let_forced = std::strcmp(v, "1") == 0;
     }
+    if (const char *v = std::getenv("BH_LANE_ORDER_SORT")) e->lane_sort = std::strcmp(v, "1") == 0;
     HIPCHK(e, hipSetDevice(device));
     HIPCHK(e, hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
     TRY(dev_alloc(e, e->scalars, 16));

@@ -2000,9 +2000,10 @@ int cell_table_depth(int J, int64_t n) {
 // The traversal's wave walks the union of its 64 lanes' interaction lists, so how bodies are
 // grouped into waves sets its work.  64 Hilbert-consecutive bodies form more compact groups than
 // 64 Morton-consecutive ones (no Z jumps): 6.5 % fewer cursor stops and 7.7 % fewer point-force
-// blocks at C3 and C4 (oracle union-walk model).  The lane map lane -> slot is made by sorting
-// the bodies by the Hilbert index of their depth-16 cell (from the Morton key of the build) and
-// carried through later builds by the builds' permutations, re-sorted every LANE_REFRESH builds.
+// blocks at C3 and C4 (oracle union-walk model).  The lane map lane -> slot lists the bodies
+// in the order of the Hilbert index of their depth-16 cell (from the Morton key of the build,
+// without its low BH_LANE_LO_BIT bits; ties in slot order) and is carried through later builds
+// by the builds' permutations, made anew every LANE_REFRESH builds.
 // It only groups bodies into waves: every body's sum is unchanged.
 __device__ __forceinline__ uint32_t hilbert16(uint64_t key, int J) {
     // de-interleave the top 16 Morton digits (digit = ix | iy << 1, root first)
@@ -2048,15 +2049,185 @@ __global__ __launch_bounds__(TB) void k_lane_remap(int64_t n, const uint32_t *__
     if (q < n) lanes[q] = inv[lanes[q]];
 }
 
-// The refresh sorts 24 bits (the depth-12 Hilbert cell: ~0.6 px at the 2400x800 root) with
-// rocprim's onesweep radix sort (3 passes) -- its merge sort, the default below 2^20 keys, took
-// ~150 us at C3.
+// The refresh orders by 24 bits (the depth-12 Hilbert cell: ~0.6 px at the 2400x800 root).
+// BH_LANE_ORDER_SORT=1 does it as it was first done, with rocprim's onesweep radix sort (3
+// passes) -- its merge sort, the default below 2^20 keys, took ~150 us at C3.
 using LaneSortConfig = rocprim::radix_sort_config<rocprim::default_config, rocprim::default_config,
                                                   rocprim::default_config, 1024>;
 #ifndef BH_LANE_LO_BIT
 #define BH_LANE_LO_BIT 8
 #endif
 constexpr unsigned LANE_SORT_LO_BIT = BH_LANE_LO_BIT;
+
+// ---- the refresh without a sort: run scatter ----------------------------------------------
+// The slots are in Morton order, and the top 2 d bits of a Hilbert index are a function of the
+// top d Morton digits.  So the slots of one sort key (hilbert16 >> LANE_SORT_LO_BIT, a Hilbert
+// cell) are one contiguous run, already in their final relative order: the stable sort only moves
+// whole runs.  The key is split into a coarse prefix (its bits above LANE_FINE_BITS: one Morton
+// cell, so one contiguous slot range and one contiguous lane range) and a fine rest.
+//   k_lane_keys    key per slot; the first / last slot of every coarse cell (plain stores: one
+//                  writer each); the slots that are not in the tree keep their place at the tail
+//   k_lane_bases   exclusive scan of the coarse cells' counts in Hilbert order: first lanes
+//   k_lane_scatter one workgroup per coarse cell: first / last slot of every run of a fine key in
+//                  LDS (again one writer each), a scan of the run lengths in fine-key order, and
+//                  lanes[cell's first lane + run's offset + slot - run's first slot] = slot
+// No atomics and nothing that depends on timing.  The sentinel slots (sorted last by the build,
+// key 0xFFFFFFFF >> LANE_SORT_LO_BIT: the last Hilbert cell's key too) never enter the tables:
+// they are lanes [live count, n) in slot order, which is where they already are.
+constexpr int LANE_KEY_BITS = 32 - (int)LANE_SORT_LO_BIT;
+// The split (C3, beside the first traversal, longest k_lane_scatter launch): 12 fine bits 102 us
+// -- 233 cells hold bodies, a disk's centre 61 000 of them, one workgroup's loop; 10 bits 45 us
+// (875 cells, 26 000); 8 bits 70 us and k_lane_bases' one workgroup 30 us over 65 536 counts
+#ifndef BH_LANE_FINE_BITS
+#define BH_LANE_FINE_BITS 10
+#endif
+constexpr int LANE_FINE_BITS = BH_LANE_FINE_BITS;
+constexpr uint32_t LANE_FINE = 1u << LANE_FINE_BITS;
+constexpr uint32_t LANE_COARSE = 1u << (LANE_KEY_BITS - LANE_FINE_BITS);
+constexpr size_t LANE_TABLE_BYTES = sizeof(uint32_t) * 3 * LANE_COARSE;  // cstart, cend, cbase
+constexpr int LANE_BASES_TB = 1024;
+constexpr int LANE_UNROLL = 4;
+static_assert(LANE_SORT_LO_BIT % 2 == 0 && LANE_FINE_BITS % 2 == 0 && LANE_FINE_BITS > 0 &&
+                  LANE_FINE_BITS < LANE_KEY_BITS,
+              "whole Morton digits");
+static_assert(LANE_COARSE % LANE_BASES_TB == 0 && (2 * LANE_COARSE) % TB == 0 && LANE_FINE % TB == 0,
+              "table sizes: whole blocks");
+
+// Morton keys with equal (key >> shift) share the coarse cell: hilbert16 has 2 lv bits, the sort
+// key drops LANE_SORT_LO_BIT of them and the coarse prefix LANE_FINE_BITS more, which leaves the
+// Hilbert cell of depth lv - (those bits) / 2 -- no bit at all on a shallow tree: one coarse cell
+inline int lane_coarse_shift(int J) {
+    const int lv = J < 16 ? J : 16;
+    const int depth = lv - ((int)LANE_SORT_LO_BIT + LANE_FINE_BITS) / 2;
+    return 2 * (J - (depth > 0 ? depth : 0));
+}
+
+__global__ __launch_bounds__(TB) void k_lane_clear(uint32_t *__restrict__ tab) {
+    chain_prio();
+    tab[blockIdx.x * TB + threadIdx.x] = 0u;  // grid: the two tables exactly
+}
+
+__global__ __launch_bounds__(TB) void k_lane_keys(int64_t n, int J, int cshift,
+                                                  const uint64_t *__restrict__ keys_s,
+                                                  uint32_t *__restrict__ hkey,
+                                                  uint32_t *__restrict__ cstart,
+                                                  uint32_t *__restrict__ cend,
+                                                  uint32_t *__restrict__ lanes) {
+    chain_prio();
+    const int64_t a = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (a >= n) return;
+    const uint64_t k = keys_s[a];
+    if (k == sentinel_key(J)) {  // not in the tree: last, in slot order
+        hkey[a] = 0xFFFFFFFFu;
+        lanes[a] = (uint32_t)a;
+        return;
+    }
+    const uint32_t h = hilbert16(k, J) >> LANE_SORT_LO_BIT;
+    hkey[a] = h;
+    const uint32_t c = h >> LANE_FINE_BITS;  // (< LANE_COARSE: h has LANE_KEY_BITS bits)
+    const uint64_t p = k >> cshift;
+    if (a == 0 || (keys_s[a - 1] >> cshift) != p) cstart[c] = (uint32_t)a;
+    if (a + 1 == n || (keys_s[a + 1] >> cshift) != p) cend[c] = (uint32_t)(a + 1);  // (a sentinel differs)
+}
+
+// block-wide exclusive scan of one value per thread (whole waves; s_wave: one word per wave)
+__device__ __forceinline__ uint32_t lane_block_scan(uint32_t v, uint32_t *s_wave) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(inc, d, 64);
+        if (lane >= d) inc += t;
+    }
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    uint32_t before = 0;
+    for (int i = 0; i < w; ++i) before += s_wave[i];
+    __syncthreads();  // (s_wave may be reused)
+    return before + inc - v;
+}
+
+__global__ __launch_bounds__(LANE_BASES_TB) void k_lane_bases(const uint32_t *__restrict__ cstart,
+                                                              const uint32_t *__restrict__ cend,
+                                                              uint32_t *__restrict__ cbase) {
+    chain_prio();
+    __shared__ uint32_t s_wave[LANE_BASES_TB / 64];
+    constexpr int PER = LANE_COARSE / LANE_BASES_TB;
+    const uint32_t c0 = threadIdx.x * PER;
+    uint32_t cnt[PER], sum = 0;
+    for (int i = 0; i < PER; ++i) {
+        cnt[i] = cend[c0 + i] - cstart[c0 + i];  // (both zero: an empty cell)
+        sum += cnt[i];
+    }
+    uint32_t run = lane_block_scan(sum, s_wave);
+    for (int i = 0; i < PER; ++i) {
+        cbase[c0 + i] = run;
+        run += cnt[i];
+    }
+}
+
+__global__ __launch_bounds__(TB) void k_lane_scatter(int64_t n, const uint32_t *__restrict__ hkey,
+                                                     const uint32_t *__restrict__ cstart,
+                                                     const uint32_t *__restrict__ cend,
+                                                     const uint32_t *__restrict__ cbase,
+                                                     uint32_t *__restrict__ lanes) {
+    chain_prio();
+    const uint32_t c = blockIdx.x;
+    const uint32_t s0 = cstart[c], s1 = cend[c];
+    if (s1 <= s0) return;  // empty (the whole block alike)
+    __shared__ uint32_t s_first[LANE_FINE], s_off[LANE_FINE];  // run's first slot; end, then offset
+    __shared__ uint32_t s_wave[TB / 64];
+    constexpr uint32_t FMASK = LANE_FINE - 1;
+    constexpr int PER = LANE_FINE / TB;
+    for (uint32_t f = threadIdx.x; f < LANE_FINE; f += TB) s_first[f] = s_off[f] = 0u;
+    __syncthreads();
+    // a heavy cell (a disk's centre) loops: the tables are per fine key, not per chunk
+    // (LANE_UNROLL slots per thread and turn: their loads are in flight together)
+    constexpr uint32_t NONE = 0xFFFFFFFFu;  // no live key (those have LANE_KEY_BITS bits)
+    for (uint32_t a0 = s0 + threadIdx.x; a0 < s1; a0 += LANE_UNROLL * TB) {
+        uint32_t hp[LANE_UNROLL], h[LANE_UNROLL], hn[LANE_UNROLL];
+#pragma unroll
+        for (int j = 0; j < LANE_UNROLL; ++j) {
+            const uint32_t a = a0 + j * TB;
+            const bool in = a < s1;
+            h[j] = in ? hkey[a] : NONE;
+            hp[j] = in && a > s0 ? hkey[a - 1] : NONE;
+            hn[j] = in && a + 1 < s1 ? hkey[a + 1] : NONE;
+        }
+#pragma unroll
+        for (int j = 0; j < LANE_UNROLL; ++j) {
+            const uint32_t a = a0 + j * TB;
+            if (a >= s1) break;
+            if (hp[j] != h[j]) s_first[h[j] & FMASK] = a;
+            if (hn[j] != h[j]) s_off[h[j] & FMASK] = a + 1;
+        }
+    }
+    __syncthreads();
+    const uint32_t f0 = threadIdx.x * PER;
+    uint32_t len[PER], sum = 0;
+    for (int i = 0; i < PER; ++i) {
+        len[i] = s_off[f0 + i] - s_first[f0 + i];
+        sum += len[i];
+    }
+    uint32_t run = cbase[c] + lane_block_scan(sum, s_wave);
+    for (int i = 0; i < PER; ++i) {
+        s_off[f0 + i] = run;  // (own entries only)
+        run += len[i];
+    }
+    __syncthreads();
+    for (uint32_t a0 = s0 + threadIdx.x; a0 < s1; a0 += LANE_UNROLL * TB) {
+        uint32_t h[LANE_UNROLL];
+#pragma unroll
+        for (int j = 0; j < LANE_UNROLL; ++j) h[j] = a0 + j * TB < s1 ? hkey[a0 + j * TB] : NONE;
+#pragma unroll
+        for (int j = 0; j < LANE_UNROLL; ++j) {
+            const uint32_t a = a0 + j * TB;
+            if (a >= s1) break;
+            const uint32_t f = h[j] & FMASK;
+            const uint32_t q = s_off[f] + (a - s_first[f]);
+            if (q < n) lanes[q] = a;  // (always, for sorted keys: the guard keeps the store in the map)
+        }
+    }
+}
 
 // The pipelined step (engine.cpp): a build made while the previous evaluation still kicks the
 // velocities leaves them out (src.vx = null); they follow with the build's permutation.
@@ -2117,17 +2288,28 @@ hipError_t lane_order(const TreeBuffers &b, int64_t n, int J, bool refresh, uint
     }
     // keys32 / keys32_s / idx are free once the build has run
     return lane_order_into(b.keys_s, n, J, b.keys32, b.keys32_s, b.idx, b.scratch, b.scratch_bytes,
-                           lanes, s);
+                           lanes, s, b.lane_sort);
 }
 
 hipError_t lane_order_into(const uint64_t *keys_s, int64_t n, int J, uint32_t *hkey,
                            uint32_t *hkey_s, uint32_t *slot, void *scratch, size_t scratch_bytes,
-                           uint32_t *lanes, hipStream_t s) {
+                           uint32_t *lanes, hipStream_t s, bool sort) {
     if (n <= 0) return hipSuccess;
-    k_hilbert_keys<<<grid_for(n), TB, 0, s>>>(n, J, keys_s, hkey, slot);
-    size_t bytes = scratch_bytes;
-    return rocprim::radix_sort_pairs<LaneSortConfig>(scratch, bytes, hkey, hkey_s, slot, lanes,
-                                                     (size_t)n, LANE_SORT_LO_BIT, 32u, s);
+    if (sort) {  // BH_LANE_ORDER_SORT=1: the stable radix sort the run scatter replaced
+        k_hilbert_keys<<<grid_for(n), TB, 0, s>>>(n, J, keys_s, hkey, slot);
+        size_t bytes = scratch_bytes;
+        return rocprim::radix_sort_pairs<LaneSortConfig>(scratch, bytes, hkey, hkey_s, slot, lanes,
+                                                         (size_t)n, LANE_SORT_LO_BIT, 32u, s);
+    }
+    if (scratch_bytes < LANE_TABLE_BYTES) return hipErrorInvalidValue;
+    uint32_t *cstart = static_cast<uint32_t *>(scratch);
+    uint32_t *cend = cstart + LANE_COARSE, *cbase = cend + LANE_COARSE;
+    const int cshift = lane_coarse_shift(J);
+    k_lane_clear<<<2 * LANE_COARSE / TB, TB, 0, s>>>(cstart);  // (cend follows cstart)
+    k_lane_keys<<<grid_for(n), TB, 0, s>>>(n, J, cshift, keys_s, hkey, cstart, cend, lanes);
+    k_lane_bases<<<1, LANE_BASES_TB, 0, s>>>(cstart, cend, cbase);
+    k_lane_scatter<<<LANE_COARSE, TB, 0, s>>>(n, hkey, cstart, cend, cbase, lanes);
+    return hipGetLastError();
 }
 
 size_t lane_sort_bytes(int64_t n) {
@@ -2136,7 +2318,7 @@ size_t lane_sort_bytes(int64_t n) {
                                                     (uint32_t *)nullptr, (uint32_t *)nullptr,
                                                     (uint32_t *)nullptr, (size_t)n,
                                                     LANE_SORT_LO_BIT, 32u);
-    return bytes;
+    return bytes > LANE_TABLE_BYTES ? bytes : LANE_TABLE_BYTES;  // either path
 }
 
 size_t tree_scratch_bytes(int64_t n, int J) {
@@ -2145,11 +2327,7 @@ size_t tree_scratch_bytes(int64_t n, int J) {
     (void)rocprim::radix_sort_pairs<SortConfig>(nullptr, sort_bytes, (uint32_t *)nullptr,
                                                 (uint32_t *)nullptr, (uint32_t *)nullptr,
                                                 (uint32_t *)nullptr, (size_t)n, 0u, 32u);
-    size_t lane_bytes = 0;
-    (void)rocprim::radix_sort_pairs<LaneSortConfig>(nullptr, lane_bytes, (uint32_t *)nullptr,
-                                                    (uint32_t *)nullptr, (uint32_t *)nullptr,
-                                                    (uint32_t *)nullptr, (size_t)n,
-                                                    LANE_SORT_LO_BIT, 32u);
+    const size_t lane_bytes = lane_sort_bytes(n);
     sort_bytes = sort_bytes > lane_bytes ? sort_bytes : lane_bytes;
     (void)rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t *)nullptr,
                                   (uint32_t *)nullptr, 0u, (size_t)(n + 1),
