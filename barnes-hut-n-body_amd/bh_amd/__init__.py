@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "bh_collective_log_clear", "bh_step_begin", "bh_step_positions", "bh_step_end",
     "bh_progress", "bh_compute_potential", "bh_compute_diagnostics", "bh_potential_kernel_ms",
     "bh_nbody3d_center_of_mass", "bh_default_view", "bh_render_bodies", "bh_render_kernel_ms",
+    "bh_launch_plan",
 )
 
 
@@ -217,6 +218,8 @@ def load_library(path: str | None = None):
                                    _I64P, _I64P]
     lib.bh_gather_slot.argtypes = [ctypes.c_int64, ctypes.c_int, ctypes.c_int64]
     lib.bh_gather_slot.restype = ctypes.c_int64
+    lib.bh_launch_plan.argtypes = [ctypes.POINTER(BhParams), ctypes.c_int64, _I64P,
+                                   ctypes.c_int64, _I64P]
     lib.bh_selftest_fast_math.argtypes = [ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, _I64P]
     _F = ctypes.POINTER(ctypes.c_float)
     lib.bh_nbody3d_create.argtypes = [ctypes.c_int, ctypes.POINTER(_VP)]
@@ -288,6 +291,29 @@ def gather_slot(n: int, world: int, lane: int) -> int:
     if g < 0:
         raise BhError(BH_E_INVALID, "bh_gather_slot: invalid arguments")
     return g
+
+
+# enum BH_PLAN_* (include/bh_engine.h), in order
+LAUNCH_PLAN_FIELDS = (
+    "small_front", "small_front_p", "cell_depth", "sort_buckets", "com_chunks", "span_groups",
+    "own_scan", "bfs", "bfs_bits", "bpw", "wpb", "xcd_groups", "kick_bpw", "kick_wpb",
+    "kick_xcd_groups", "order_runs",
+)
+
+
+def launch_plan(n: int, params: BhParams | None = None) -> dict:
+    """The kernels and launch shapes the one-GPU step picks for a list of `n` bodies
+    (bh_launch_plan; host-only, no device): a dict keyed by LAUNCH_PLAN_FIELDS."""
+    p = params if params is not None else default_params()
+    out = np.zeros(len(LAUNCH_PLAN_FIELDS), dtype=np.int64)
+    got = ctypes.c_int64(0)
+    rc = load_library().bh_launch_plan(ctypes.byref(p), int(n), out.ctypes.data_as(_I64P),
+                                       out.size, ctypes.byref(got))
+    if rc != BH_OK:
+        raise BhError(rc, "bh_launch_plan: invalid arguments")
+    if got.value != out.size:
+        raise BhError(BH_E_INVALID, "bh_launch_plan: field list out of date")
+    return {k: int(v) for k, v in zip(LAUNCH_PLAN_FIELDS, out)}
 
 
 class NBody3D:

@@ -54,6 +54,9 @@ constexpr int COM_CHUNK_SHIFT = BH_COM_CHUNK_SHIFT;
 __host__ __device__ inline uint32_t span_stride_for(int64_t n) {
     return (uint32_t)((n >> COM_CHUNK_SHIFT) + 2);
 }
+__host__ __device__ inline int64_t com_chunks(int64_t n) {  // k_emit_com's workgroups
+    return (n + (1 << COM_CHUNK_SHIFT) - 1) >> COM_CHUNK_SHIFT;
+}
 // chunk boundaries are grouped by 1024 (one span workgroup each, tree_build.hip)
 __host__ __device__ inline uint32_t span_groups(uint32_t span_stride) {
     return (span_stride + 1023) / 1024;
@@ -319,6 +322,14 @@ struct TreeBuffers {
 };
 
 int cell_table_depth(int J, int64_t n);
+// The size switches of tree_build (host-only; tree_build branches on them, bh_launch_plan
+// reports them).  small_front_for: the one-workgroup front runs for n bodies once a build has left
+// splitters, with P = the next power of two of n.  base_scan_sums_bytes: the block sums k_prep
+// leaves for the build's own scan of the node counts (part of tree_scratch_bytes);
+// own_base_scan: that scan runs instead of rocprim's, given the scratch at hand.
+bool small_front_for(int64_t n, uint32_t &P);
+size_t base_scan_sums_bytes(int64_t n);
+bool own_base_scan(int64_t n, size_t scratch_bytes);
 size_t tree_scratch_bytes(int64_t n, int J);
 hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStream_t s);
 // Splitters spl[from, to) for a bucket sort over more slots than the build that wrote spl[0,
@@ -407,6 +418,20 @@ size_t wave_order_runs(int64_t n);  // runs of a launch over n lanes (0: too man
 // Whether traverse() walks [lo, hi) breadth first, one body per wave (traverse.hip bfs_walk)
 bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting);
 hipError_t wave_order(const uint32_t *cost, int64_t n, uint32_t *order, hipStream_t s);
+// What traverse() launches for [lo, hi) (host-only; traverse() itself launches from it, and
+// bh_launch_plan reports it).  ordered: a WaveOrder with an order is passed.
+struct TraverseShape {
+    bool bfs;           // breadth-first walk, one body per wave
+    uint32_t bm_words;  // its bitmap over node indices, in 32-bit words (0: cursor walk)
+    uint32_t bpw;       // bodies per wave
+    uint32_t waves;     // waves of the launch (whole XCD runs when ordered)
+    bool ordered;       // the wave order is applied
+    uint32_t wpb;       // waves per workgroup
+    uint32_t groups;    // workgroups (the grid)
+    uint32_t xcd_full;  // whole groups of workgroups that k_traverse remaps across the XCDs
+};
+TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
+                             bool ordered);
 void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x, double *y,
               const double *m, const uint32_t *cidx, int64_t lo, int64_t hi, const Geometry &g,
               const ForceParams &fp, double *a2, const TraverseCounters *cnt,

@@ -1495,9 +1495,13 @@ int evaluate_let(bh_engine *e, KickMode kick, bool *done) {
 #ifndef BH_LPT_MIN_LANES
 #define BH_LPT_MIN_LANES 131072
 #endif
+bool wave_order_used(int64_t lanes) {
+    return BH_TRAV_LPT && lanes >= BH_LPT_MIN_LANES && wave_order_runs(lanes) != 0;
+}
+
 int wave_order_for(bh_engine *e, int slot, int64_t lanes, hipStream_t s, WaveOrder &wo) {
     wo = WaveOrder{};
-    if (!BH_TRAV_LPT || lanes < BH_LPT_MIN_LANES || wave_order_runs(lanes) == 0) return BH_OK;
+    if (!wave_order_used(lanes)) return BH_OK;
     uint32_t *cost = e->wave_cost + slot * e->cost_stride;
     uint32_t *order = e->run_order + slot * e->order_stride;
     if (e->order_n[slot] != lanes) {  // the order must be a permutation of this launch's runs
@@ -4044,6 +4048,42 @@ int bh_shard_range(int64_t n, int rank, int world, int round, int64_t *lo, int64
 int64_t bh_gather_slot(int64_t n, int world, int64_t lane) {
     if (n < 0 || world < 1 || lane < 0) return -1;
     return gather_slot(shard_layout(n, world), lane);
+}
+
+// Every value comes from the function the build or the traversal itself branches on.
+int bh_launch_plan(const bh_params *p, int64_t n, int64_t *out, int64_t cap, int64_t *n_out) {
+    if (!p || n < 0 || !n_out || cap < 0 || (cap > 0 && !out)) return BH_E_INVALID;
+    *n_out = BH_PLAN_FIELDS;
+    Geometry g;
+    std::string err;
+    if (make_geometry(*p, g, err) != BH_OK) return BH_E_INVALID;
+    int64_t f[BH_PLAN_FIELDS] = {};
+    if (n > 0) {
+        uint32_t P = 0;
+        f[BH_PLAN_SMALL_FRONT] = small_front_for(n, P) ? 1 : 0;
+        f[BH_PLAN_SMALL_FRONT_P] = f[BH_PLAN_SMALL_FRONT] ? (int64_t)P : 0;
+        f[BH_PLAN_CELL_DEPTH] = cell_table_depth(g.J, n);
+        f[BH_PLAN_SORT_BUCKETS] = sort_buckets(n);
+        f[BH_PLAN_COM_CHUNKS] = com_chunks(n);
+        f[BH_PLAN_SPAN_GROUPS] = span_groups(span_stride_for(n));  // (capacity = n)
+        // (the scratch of any engine holds at least the block sums: tree_scratch_bytes)
+        f[BH_PLAN_OWN_SCAN] = own_base_scan(n, base_scan_sums_bytes(n)) ? 1 : 0;
+        const size_t ncap = node_capacity(n, g.J);
+        const bool ordered = wave_order_used(n);
+        const TraverseShape t1 = traverse_shape(ncap, 0, n, KICK_DRIFT, false, ordered);
+        const TraverseShape t2 = traverse_shape(ncap, 0, n, KICK_ONLY, false, ordered);
+        f[BH_PLAN_BFS] = t1.bfs ? 1 : 0;
+        f[BH_PLAN_BFS_BITS] = 32 * (int64_t)t1.bm_words;
+        f[BH_PLAN_BPW] = t1.bpw;
+        f[BH_PLAN_WPB] = t1.wpb;
+        f[BH_PLAN_XCD_GROUPS] = t1.xcd_full;
+        f[BH_PLAN_KICK_BPW] = t2.bpw;
+        f[BH_PLAN_KICK_WPB] = t2.wpb;
+        f[BH_PLAN_KICK_XCD_GROUPS] = t2.xcd_full;
+        f[BH_PLAN_ORDER_RUNS] = (int64_t)wave_order_runs(n);
+    }
+    for (int64_t i = 0; i < cap && i < BH_PLAN_FIELDS; ++i) out[i] = f[i];
+    return BH_OK;
 }
 
 int bh_selftest_fast_math(int device, int64_t n, uint64_t seed, int64_t *mismatches) {

@@ -37,6 +37,14 @@ constexpr int TB = 64;  // one wave per workgroup: finest dispatch granularity (
 // the same node records.
 constexpr int MAX_WPB = 8;
 static_assert(BH_TRAV_XCD_RUN % MAX_WPB == 0, "an XCD run holds whole workgroups");
+// Workgroups of one remapped group (8 XCDs x one run each) and the whole groups of a grid: the
+// tail past them keeps its dispatch order (k_traverse, bh_launch_plan).
+__host__ __device__ constexpr uint32_t xcd_group_blocks(uint32_t wpb) {
+    return 8u * (BH_TRAV_XCD_RUN / wpb);
+}
+__host__ __device__ constexpr uint32_t xcd_full_groups(uint32_t groups, uint32_t wpb) {
+    return groups / xcd_group_blocks(wpb);
+}
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
@@ -630,7 +638,8 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_traverse(const Node *__restric
     // xcd_block() with runs of BH_TRAV_XCD_RUN / wpb workgroups (= BH_TRAV_XCD_RUN waves)
     uint32_t b = blockIdx.x;
     {
-        const uint32_t C = BH_TRAV_XCD_RUN / wpb, G = 8 * C, full = gridDim.x / G;
+        const uint32_t C = BH_TRAV_XCD_RUN / wpb, G = xcd_group_blocks(wpb);
+        const uint32_t full = xcd_full_groups(gridDim.x, wpb);
         if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
     }
     uint32_t v = b * wpb + (threadIdx.x >> 6);
@@ -833,6 +842,30 @@ bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, boo
            kick_mode != KICK_OWN_DRIFT && kick_mode != KICK_OWN_ONLY;
 }
 
+// The launch shape of traverse() over [lo, hi): the one place that picks it (bh_launch_plan reads
+// it out through the same call).
+TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
+                             bool ordered) {
+    TraverseShape t{};
+    if (hi <= lo) return t;
+    t.bfs = traverse_is_bfs(node_cap, lo, hi, kick_mode, counting);
+    if (t.bfs) {
+        // (a one-GPU tree has ~1.7 nodes per body: C1 21 565 for 12 500, 3 511 for 2 000)
+        const size_t bits = std::min<size_t>(node_cap, (size_t)(9 * (hi - lo) / 4 + 256));
+        t.bm_words = (uint32_t)std::min<size_t>((bits + 31) / 32, BFS_MAX_BM_WORDS);
+    }
+    // (the counting walk keeps 64 bodies per wave: its per-wave counters define lane efficiency)
+    t.bpw = counting ? (uint32_t)TB : t.bfs ? 1u : bodies_per_wave(hi - lo);
+    t.waves = (uint32_t)((hi - lo + t.bpw - 1) / t.bpw);
+    t.ordered = ordered && t.bpw == TB && wave_order_runs(hi - lo);
+    if (t.ordered)  // whole runs: every run index the order maps to exists in the grid
+        t.waves = (uint32_t)(wave_order_runs(hi - lo) * BH_TRAV_XCD_RUN);
+    t.wpb = waves_per_group(t.waves, t.bpw);
+    t.groups = (t.waves + t.wpb - 1) / t.wpb;
+    t.xcd_full = xcd_full_groups(t.groups, t.wpb);
+    return t;
+}
+
 void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x, double *y,
               const double *m, const uint32_t *cidx, int64_t lo, int64_t hi, const Geometry &g,
               const ForceParams &fp, double *a2, const TraverseCounters *cnt,
@@ -840,21 +873,12 @@ void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x
     if (hi <= lo) return;
     // node records addressed by a 32-bit byte offset while the array stays below 4 GiB
     const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
-    const bool bfs = traverse_is_bfs(node_cap, lo, hi, kick ? kick->mode : KICK_NONE, cnt);
-    uint32_t bm_words = 0;
-    if (bfs) {
-        // (a one-GPU tree has ~1.7 nodes per body: C1 21 565 for 12 500, 3 511 for 2 000)
-        const size_t bits = std::min<size_t>(node_cap, (size_t)(9 * (hi - lo) / 4 + 256));
-        bm_words = (uint32_t)std::min<size_t>((bits + 31) / 32, BFS_MAX_BM_WORDS);
-    }
-    // (the counting walk keeps 64 bodies per wave: its per-wave counters define lane efficiency)
-    const uint32_t bpw = cnt ? (uint32_t)TB : bfs ? 1u : bodies_per_wave(hi - lo);
-    unsigned grid = (unsigned)((hi - lo + bpw - 1) / bpw);  // waves
-    const WaveOrder w = wo && bpw == TB && wave_order_runs(hi - lo) ? *wo : WaveOrder{};
-    if (w.order)  // whole runs: every run index the order maps to exists in the grid
-        grid = (unsigned)(wave_order_runs(hi - lo) * BH_TRAV_XCD_RUN);
-    const uint32_t wpb = waves_per_group(grid, bpw);
-    grid = (grid + wpb - 1) / wpb;  // workgroups
+    const TraverseShape t = traverse_shape(node_cap, lo, hi, kick ? kick->mode : KICK_NONE,
+                                           cnt != nullptr, wo && wo->order);
+    const bool bfs = t.bfs;
+    const uint32_t bm_words = t.bm_words, bpw = t.bpw, wpb = t.wpb;
+    const unsigned grid = t.groups;  // workgroups
+    const WaveOrder w = t.ordered ? *wo : WaveOrder{};
     const size_t lds = bfs ? bfs_lds_bytes(bm_words) : 0;
     const KickArgs ka = kick ? *kick : KickArgs{KICK_NONE, nullptr, nullptr, 0.0, 0.0, nullptr};
     const TraverseCounters tc = cnt ? *cnt : TraverseCounters{nullptr, nullptr, nullptr, nullptr};

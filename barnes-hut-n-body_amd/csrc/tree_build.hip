@@ -1996,6 +1996,21 @@ int cell_table_depth(int J, int64_t n) {
     return d < J ? d : J;
 }
 
+bool small_front_for(int64_t n, uint32_t &P) { return small_front(n, P); }
+
+inline int64_t prep_blocks_for(int64_t n) { return (n + 1 + TB - 1) / TB; }  // k_prep's grid
+
+size_t base_scan_sums_bytes(int64_t n) {
+    return sizeof(uint32_t) * (size_t)(prep_blocks_for(n) + 1);
+}
+
+// (above 4 M counts rocprim's single pass is faster: the blocks' prefix reads grow with n^2 /
+// block size -- C4 16.52-16.54 against 16.57-16.58 ms per step, profiles/r05y4_ab_c4.txt)
+bool own_base_scan(int64_t n, size_t scratch_bytes) {
+    return BH_BASE_SCAN && n + 1 <= ((int64_t)1 << 22) &&
+           scratch_bytes >= sizeof(uint32_t) * (size_t)prep_blocks_for(n);
+}
+
 // ---- Hilbert lane order for the traversal (traverse.hip) ---------------------------------
 // The traversal's wave walks the union of its 64 lanes' interaction lists, so how bodies are
 // grouped into waves sets its work.  64 Hilbert-consecutive bodies form more compact groups than
@@ -2332,7 +2347,7 @@ size_t tree_scratch_bytes(int64_t n, int J) {
     (void)rocprim::exclusive_scan(nullptr, scan_bytes, (const uint32_t *)nullptr,
                                   (uint32_t *)nullptr, 0u, (size_t)(n + 1),
                                   rocprim::plus<uint32_t>());
-    const size_t tsum_bytes = sizeof(uint32_t) * (size_t)((n + 1 + TB - 1) / TB + 1);  // k_prep
+    const size_t tsum_bytes = base_scan_sums_bytes(n);  // k_prep
     scan_bytes = scan_bytes > tsum_bytes ? scan_bytes : tsum_bytes;
     return sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
 }
@@ -2387,11 +2402,8 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
             n, g.J, D0, b.keys32_s, b.keys_s, b.perm, b.cell_start, b.super_list, n_super);
     else
         k_key_fixup<<<grid_for(n), TB, 0, s>>>(n, g.J, b.keys32_s, b.keys_s, b.perm);
-    const int64_t prep_blocks = (n + 1 + TB - 1) / TB;
-    // (above 4 M counts rocprim's single pass is faster: the blocks' prefix reads grow with n^2 /
-    // block size -- C4 16.52-16.54 against 16.57-16.58 ms per step, profiles/r05y4_ab_c4.txt)
-    const bool own_scan = BH_BASE_SCAN && n + 1 <= ((int64_t)1 << 22) &&
-                          b.scratch_bytes >= sizeof(uint32_t) * (size_t)prep_blocks;
+    const int64_t prep_blocks = prep_blocks_for(n);
+    const bool own_scan = own_base_scan(n, b.scratch_bytes);
     uint32_t *tsum = own_scan ? static_cast<uint32_t *>(b.scratch) : nullptr;
     if (!small)
         k_prep<<<(unsigned)prep_blocks, TB, 0, s>>>(n, g.J, b.keys_s, b.perm, b.src, b.dst, b.cpl,
@@ -2411,7 +2423,7 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
     if (!BH_FIXUP_CELLS && !small)
         k_cells<<<grid_for(nbins1), TB, 0, s>>>(n, g.J, D0, b.keys_s, b.cell_start, b.super_list,
                                                 n_super);
-    k_emit_com<<<(unsigned)((n + (1 << COM_CHUNK_SHIFT) - 1) >> COM_CHUNK_SHIFT), EC_TB, 0, s>>>(
+    k_emit_com<<<(unsigned)com_chunks(n), EC_TB, 0, s>>>(
         n, g, D0, b.keys_s, b.cpl, b.base, b.cell_start, b.dst.x, b.dst.y, b.dst.m, b.dst.cidx,
         b.idx, b.nodes, b.scalars + 1, b.keys32, b.lanes_remap,
         SpanOut{b.span_list, b.span_stride, b.super_list, n_groups}, b.tc);

@@ -397,6 +397,34 @@ int bh_set_profiling(bh_engine *e, int enabled);
 int bh_shard_range(int64_t n, int rank, int world, int round, int64_t *lo, int64_t *hi);
 int64_t bh_gather_slot(int64_t n, int world, int64_t lane);
 
+/* The kernels and launch shapes that the one-GPU step picks from the list size alone, read out
+ * for a fresh engine with these parameters after bh_reset_bodies(n) (capacity = n).  Host-only:
+ * no device, no handle.  Each value is returned by the function that the tree build or the
+ * traversal itself branches on, so the read-out moves with the code; tests take their sizes from
+ * where it changes.  out receives min(cap, BH_PLAN_FIELDS) values, *n_out = BH_PLAN_FIELDS;
+ * n = 0: all zero.  The build's fields describe every build after an engine's first (which has
+ * no splitters yet and sorts with the library's radix sort). */
+enum {
+    BH_PLAN_SMALL_FRONT = 0, /* 1: the build's front (keys, sort, prefix lengths) is one workgroup */
+    BH_PLAN_SMALL_FRONT_P,   /* its sort width, the next power of two >= n (0: front is off)      */
+    BH_PLAN_CELL_DEPTH,      /* D0, the depth of the cell-start table                              */
+    BH_PLAN_SORT_BUCKETS,    /* buckets of the adaptive bucket sort                                */
+    BH_PLAN_COM_CHUNKS,      /* centre-of-mass chunks (workgroups of the node emission)           */
+    BH_PLAN_SPAN_GROUPS,     /* groups of chunk boundaries (above 1: the top span pass runs)      */
+    BH_PLAN_OWN_SCAN,        /* 1: the build's own scan of the node counts, 0: the library's      */
+    BH_PLAN_BFS,             /* 1: the step's first walk (kick and drift) is breadth first         */
+    BH_PLAN_BFS_BITS,        /* node indices its bitmap covers (a larger tree: cursor walk)       */
+    BH_PLAN_BPW,             /* first walk: bodies per wave                                        */
+    BH_PLAN_WPB,             /* first walk: waves per workgroup                                    */
+    BH_PLAN_XCD_GROUPS,      /* first walk: whole groups of workgroups remapped across the XCDs   */
+    BH_PLAN_KICK_BPW,        /* kick-only walk: bodies per wave                                    */
+    BH_PLAN_KICK_WPB,        /* kick-only walk: waves per workgroup                                */
+    BH_PLAN_KICK_XCD_GROUPS, /* kick-only walk: whole remapped groups (the tail is not remapped)  */
+    BH_PLAN_ORDER_RUNS,      /* runs of waves that a wave order would permute (0: too many)       */
+    BH_PLAN_FIELDS
+};
+int bh_launch_plan(const bh_params *p, int64_t n, int64_t *out, int64_t cap, int64_t *n_out);
+
 /* Diagnostic: checks, on HIP device `device`, the traversal's reduced-range exact sequences
  * for sqrt(d2), 1/sqrt(d2) and 1/d2 (traverse.hip) bit-for-bit against the IEEE operations on
  * n generated operands (random, near powers of two, near perfect squares, physical range);
