@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = (
     "bh_collective_log_clear", "bh_step_begin", "bh_step_positions", "bh_step_end",
     "bh_progress", "bh_compute_potential", "bh_compute_diagnostics", "bh_potential_kernel_ms",
     "bh_nbody3d_center_of_mass", "bh_default_view", "bh_render_bodies", "bh_render_kernel_ms",
-    "bh_launch_plan",
+    "bh_launch_plan", "bh_render_quads", "bh_render_quads_kernel_ms",
 )
 
 
@@ -199,6 +199,9 @@ def load_library(path: str | None = None):
                                      ctypes.POINTER(ctypes.c_uint32)]
     lib.bh_render_kernel_ms.argtypes = [_VP, _D]
     lib.bh_get_quads.argtypes = [_VP, _D, _D, _D, ctypes.c_int64, _I64P]
+    lib.bh_render_quads.argtypes = [_VP, ctypes.POINTER(BhView), ctypes.POINTER(ctypes.c_uint32),
+                                    _I64P]
+    lib.bh_render_quads_kernel_ms.argtypes = [_VP, _D]
     lib.bh_last_timings.argtypes = [_VP, _D]
     lib.bh_last_tree_nodes.argtypes = [_VP]
     lib.bh_last_tree_nodes.restype = ctypes.c_int64
@@ -694,6 +697,40 @@ class Engine:
         self._check(self._lib.bh_get_quads(self._h, _dp(cx), _dp(cy), _dp(h), n, ctypes.byref(need)))
         return cx, cy, h
 
+    def render_quads(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,
+                     heavy_mass=1000.0, lines=True, out=None):
+        """bh_render_quads: NBodyPanel.paintComponent's quadtree overlay (PNL:326-344) over the
+        cells get_quads() would return, rasterised on the device.  Returns (lines, n_quads):
+        `lines`, uint32 of shape (height, width), counts the line draws that cover each pixel (a
+        cell's corner counts 2); n_quads is len(get_quads()[0]).  lines=None (or False): the count
+        only, (None, n_quads), and no image work.  width and height default to the engine's
+        width_px and height_px.  out: a C-contiguous uint32 array of that shape to fill instead
+        of a new one.  State semantics are get_quads()': a dropped tree cache is rebuilt, and
+        that build's jitter moves bodies."""
+        v = BhView(float(view_x), float(view_y), float(zoom),
+                   int(self.params.width_px if width is None else width),
+                   int(self.params.height_px if height is None else height), float(heavy_mass))
+        want = lines is not None and lines is not False
+        ok = 1 <= v.width <= 16384 and 1 <= v.height <= 16384  # (else refused below: no plane)
+        shape = (v.height, v.width) if ok else (1, 1)
+        img = None
+        if want:
+            img = out if out is not None else np.empty(shape, dtype=np.uint32)
+            if img.shape != shape or img.dtype != np.uint32 or not img.flags.c_contiguous:
+                raise ValueError(f"out must be a C-contiguous uint32 array of shape {shape}")
+        n = ctypes.c_int64(0)
+        self._check(self._lib.bh_render_quads(
+            self._h, ctypes.byref(v),
+            img.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if want else None,
+            ctypes.byref(n)))
+        return img, int(n.value)
+
+    def render_quads_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last render_quads' kernels (bh_render_quads_kernel_ms)."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.bh_render_quads_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def let_stats(self):
         """Multi-rank build sharding: LET builds, full builds, last subset size, last LET nodes."""
         out = np.zeros(5, dtype=np.int64)
@@ -921,6 +958,15 @@ class PhysicsEngine:
             self._push()
         return self._eng.render_bodies(view_x, view_y, zoom, width, height, heavy_mass,
                                        owner=owner, counts=counts)
+
+    def render_tree(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None):
+        """NBodyPanel.paintComponent's quadtree overlay of getTreeForDebug()'s tree
+        (Engine.render_quads): (lines, n_quads).  As get_tree_for_debug, a fresh tree's jitter
+        is written back into the Body objects."""
+        self._eng.set_params(self._params())
+        got = self._eng.render_quads(view_x, view_y, zoom, width, height)
+        self._pull()
+        return got
 
     getBodies = get_bodies
     resetBodies = reset_bodies

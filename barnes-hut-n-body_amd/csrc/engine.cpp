@@ -38,6 +38,7 @@
 #include "bh_device.hpp"
 #include "bh_engine.h"
 #include "multi.hpp"
+#include "render_quads.hpp"
 #include "render_view.hpp"
 
 using namespace bh;
@@ -235,6 +236,17 @@ struct bh_engine {
     bool rnd_clean = false;
     hipEvent_t rnd_ev[2] = {nullptr, nullptr};  // around the last render's two kernels
     bool rnd_timed = false;
+
+    // bh_render_quads (render_quads.hip): buffers of its own, allocated on first use, kept while
+    // the pixel count is unchanged.  The three working planes are zero between calls (the scans
+    // re-zero what the cell kernel touched); qd_clean = false: a call failed in between
+    uint32_t *qd_rowd = nullptr, *qd_cold = nullptr, *qd_dir = nullptr;
+    uint32_t *qd_out = nullptr;               // the staged count plane, device
+    unsigned long long *qd_count = nullptr;   // the cell count in partial sums, device
+    size_t qd_pix = 0;  // pixels the planes above are sized for
+    bool qd_clean = false;
+    hipEvent_t qd_ev[2] = {nullptr, nullptr};  // around the last call's kernels
+    bool qd_timed = false;
 
     bool tree_valid = false;  // lastTree (BHA:304): keys_s / cpl / base / nodes are current
     // Multi-rank engines end a call with a LET build too; lastTree is then built on demand by
@@ -3123,12 +3135,15 @@ void bh_destroy(bh_engine *e) {
                     e->lt_x, e->lt_y, e->a2_alt, e->lt_keys, e->lt_cpl, e->lt_base, e->mir_stage,
                     e->mir_keep, e->mir_pos, e->mir_tmp, e->mir_idx_stage, e->lanes_next, e->lr_hkey, e->lr_hkey_s,
                     e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
-                    e->rnd_pixels, e->rnd_owner, e->rnd_counts};
+                    e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
+                    e->qd_out, e->qd_count};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (hipEvent_t ev : e->pot_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->rnd_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->qd_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
@@ -3937,6 +3952,105 @@ int bh_get_quads(bh_engine *e, double *cx, double *cy, double *h, int64_t cap, i
     if (w.rc != BH_OK) return w.rc;
     if (n_out) *n_out = w.k;
     return w.k > cap ? BH_E_CAPACITY : BH_OK;
+}
+
+// The overlay's working planes (zero between calls), the staged count plane and the events.
+static int quads_buffers(bh_engine *e, size_t npix, bool image, bool direct) {
+    if (image && npix != e->qd_pix) {  // another view size: made anew
+        uint32_t **all[] = {&e->qd_rowd, &e->qd_cold, &e->qd_dir, &e->qd_out};
+        for (uint32_t **q : all) {
+            if (*q) (void)hipFree(*q);
+            *q = nullptr;
+        }
+        e->qd_pix = npix;
+    }
+    if (image) {
+        uint32_t **work[] = {&e->qd_rowd, &e->qd_cold, direct ? &e->qd_dir : nullptr};
+        for (uint32_t **q : work) {
+            if (!q || *q) continue;
+            TRY(dev_alloc(e, *q, npix));
+            HIPCHK(e, hipMemsetAsync(*q, 0, sizeof(uint32_t) * npix, e->stream));
+        }
+        if (!e->qd_out) TRY(dev_alloc(e, e->qd_out, npix));
+        if (!e->qd_clean) {  // a call that failed between its kernels left the planes as they were
+            for (uint32_t *q : {e->qd_rowd, e->qd_cold, e->qd_dir})
+                if (q) HIPCHK(e, hipMemsetAsync(q, 0, sizeof(uint32_t) * npix, e->stream));
+            e->qd_clean = true;
+        }
+    }
+    if (!e->qd_count) TRY(dev_alloc(e, e->qd_count, (size_t)QUADS_COUNT_WORDS));
+    for (hipEvent_t &ev : e->qd_ev)
+        if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return BH_OK;
+}
+
+// The tree bh_get_quads walks (after the same quads_prepare), rasterised on the device.
+static int render_quads_state(bh_engine *e, const bh_view &v, uint32_t *lines, int64_t *n_quads) {
+    const size_t npix = (size_t)v.width * (size_t)v.height;
+    // BH_QUADS_DIRECT=0: one-pixel cells through the difference planes too (A/B; the same bytes).
+    // Read per call, so that one process can interleave the two (tools/quads_bench.py).
+    const char *env = std::getenv("BH_QUADS_DIRECT");
+    const bool direct = env ? std::atoi(env) != 0 : true;
+    // BH_QUADS_COMBINE=0: every one-pixel cell issues its own atomic (A/B; the same bytes)
+    env = std::getenv("BH_QUADS_COMBINE");
+    const bool combine = env ? std::atoi(env) != 0 : true;
+    TRY(quads_buffers(e, npix, lines != nullptr, direct));
+    // lastTree kept aside by a pipelined last step, or the tree in the build buffers
+    const bool aside = e->tree_valid && e->lt_aside;
+    const QuadTree t{aside ? e->lt_keys : e->keys_s, aside ? e->lt_cpl : e->cpl,
+                     aside ? e->lt_base : e->base, aside ? e->nodes_alt : e->nodes, e->n};
+    unsigned long long part[QUADS_COUNT_WORDS];
+    HIPCHK(e, hipMemsetAsync(e->qd_count, 0, sizeof(part), e->stream));
+    if (lines) e->qd_clean = false;
+    HIPCHK(e, hipEventRecord(e->qd_ev[0], e->stream));
+    quads_render(t, e->geo, v, e->qd_rowd, e->qd_cold, direct ? e->qd_dir : nullptr, combine,
+                 lines ? e->qd_out : nullptr, e->qd_count, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->qd_ev[1], e->stream));
+    if (lines) e->qd_clean = true;
+    e->qd_timed = true;
+    if (lines)
+        HIPCHK(e, hipMemcpyAsync(lines, e->qd_out, sizeof(uint32_t) * npix, hipMemcpyDeviceToHost,
+                                 e->stream));
+    HIPCHK(e, hipMemcpyAsync(part, e->qd_count, sizeof(part), hipMemcpyDeviceToHost, e->stream));
+    SYNC(e, e->stream);
+    unsigned long long cells = 0;
+    for (int k = 0; k < QUADS_COUNT_STRIPES; ++k) cells += part[k * QUADS_COUNT_STRIDE];
+    if (n_quads) *n_quads = (int64_t)cells;
+    return BH_OK;
+}
+
+int bh_render_quads(bh_engine *e, const bh_view *v, uint32_t *lines, int64_t *n_quads) {
+    if (!e || !v) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (const char *why = view_error(*v)) {
+        e->err = why;
+        return BH_E_INVALID;
+    }
+    if (e->multi) {  // as bh_get_quads: every member prepares the tree, member 0 answers
+        const int rc = multi_fan(e, [](bh_engine *m, int) {
+            TRY(comm_refused(m));
+            return fail_multi_rank(m, quads_prepare(m));
+        }, false);
+        if (rc != BH_OK) return rc;
+        const int rc0 = bh_render_quads(MULTI_M0(e), v, lines, n_quads);
+        if (rc0 != BH_OK) e->err = bh_last_error(MULTI_M0(e));
+        return rc0;
+    }
+    COMM_GUARD(e);
+    TRY(fail_multi_rank(e, quads_prepare(e)));
+    return render_quads_state(e, *v, lines, n_quads);
+}
+
+int bh_render_quads_kernel_ms(const bh_engine *e, double *ms) {
+    if (!e || !ms) return BH_E_INVALID;
+    e = MULTI_M0(e);
+    *ms = 0.0;
+    if (!e->qd_timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, e->qd_ev[0], e->qd_ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *ms = (double)f;
+    return BH_OK;
 }
 
 int bh_last_removed(const bh_engine *e, int64_t *idx, int64_t cap, int64_t *n_out) {

@@ -204,6 +204,17 @@ BHTree PhysicsEngine::getTreeForDebug() {
     return BHTree(std::move(quads));
 }
 
+int64_t PhysicsEngine::renderTree(const bh_view &view, std::vector<uint32_t> &lines) {
+    pushParams();
+    const bool sized = view.width > 0 && view.width <= 16384 && view.height > 0 &&
+                       view.height <= 16384;  // (else the call refuses the view)
+    lines.assign(sized ? (size_t)view.width * (size_t)view.height : 1, 0u);
+    int64_t cells = 0;
+    check(bh_render_quads(eng_, &view, lines.data(), &cells));
+    pullBodies(false);  // building a fresh tree can jitter positions (BHA:146-151)
+    return cells;
+}
+
 bh_diagnostics PhysicsEngine::diagnostics(bool potential) {
     pushParams();
     if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits

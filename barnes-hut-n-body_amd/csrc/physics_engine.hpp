@@ -72,6 +72,10 @@ public:
     const std::vector<Body> &getBodies() const;       // BHA:335
     void resetBodies(std::vector<Body> &newBodies);   // BHA:342-349
     BHTree getTreeForDebug();                         // BHA:329-332
+    // The panel's overlay of that tree (PNL:326-344) as line-draw counts per pixel, rasterised
+    // on the device (bh_render_quads): lines is resized to height x width, row-major; returns the
+    // number of cells.  As getTreeForDebug, a fresh tree's jitter is written back into the list.
+    int64_t renderTree(const bh_view &view, std::vector<uint32_t> &lines);
     // Conservation read-out of the caller's list (bh_compute_diagnostics; no reference
     // counterpart).  potential = true builds a tree as step()'s first half does -- its jitter is
     // written back into the list -- and adds the potential energy; false only reads the state.

@@ -200,7 +200,8 @@ int bh_step(bh_engine *e, int32_t k);
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
  * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
- * bh_last_removed, bh_map_bodies, ... as after bh_step).
+ * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
+ * way, as bh_get_quads is.
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
  * once its last merge rule is done, before its last traversal; else when the call ends -- and
  * returns the mirror planes x, y, m of the list after the call (n_out bodies; the other buffer
@@ -340,6 +341,44 @@ int bh_last_removed(const bh_engine *e, int64_t *idx, int64_t cap, int64_t *n_ou
  * (cx, cy, h) of the last tree, or of a freshly built one if the cache was dropped
  * (after resetBodies or a merge, BHA:348,526).  BH_E_CAPACITY + *n_out if cap too small. */
 int bh_get_quads(bh_engine *e, double *cx, double *cy, double *h, int64_t cap, int64_t *n_out);
+
+/* The quadtree overlay of a frame, rasterised on the device: what NBodyPanel.paintComponent draws
+ * for getTreeForDebug().visitQuads (key D, PNL:326-344), returned as one plane of line-draw counts
+ * instead of a list of cells.  Nothing of the tree is copied to the host.
+ * For every cell q that bh_get_quads would return (BHA:265-274), in binary64 with Kotlin's
+ * Double.toInt() (NaN gives 0, otherwise truncation toward zero, saturating at the Int range):
+ *     x = toInt(((q.cx - q.h) - view_x) * zoom)
+ *     y = toInt(((q.cy - q.h) - view_y) * zoom)
+ *     s = toInt(q.h * 2.0 * zoom)
+ * and the panel draws drawLine(x, y, x, y + s) and drawLine(x, y, x + s, y) (PNL:335-339):
+ * one-pixel lines, end points included, clipped to width x height.
+ *   lines[p]   (row-major height x width) the number of those line draws that cover pixel p; a
+ *              cell's corner pixel counts 2.  The panel draws with a translucent colour (alpha 180,
+ *              PNL:330): what it shows at p is that colour composited lines[p] times, so the
+ *              count is the complete picture and does not depend on the order of the cells.
+ *              NULL: only the count is produced and no image work is launched.
+ *   *n_quads   (nullable) the number of cells: bh_get_quads' *n_out.  N = 0 gives 1, the root.
+ * x + s and y + s are formed in 64-bit integers.  That equals the reference wherever Kotlin's Int
+ * addition does not overflow -- it cannot for the panel's zoom range 1..10 (PNL:56-57) with the
+ * view clamped to the world (PNL:121-128); where it would, the contract is the unwrapped line.
+ * Truncation is not floor: a cell edge up to one pixel left of or above the view lands in column
+ * or row 0, and so does a NaN view origin, as for bh_render_bodies.
+ * State and errors are exactly bh_get_quads': the tree is the last tree (lastTree, BHA:435; the
+ * copy a pipelined call kept aside included), or, if the cache was dropped, a freshly built one
+ * whose jitter moves the bodies as getTreeForDebug's does; on a multi-rank engine the lazy full
+ * build; a multi-device handle prepares on every member and answers from member 0.
+ * bh_render_quads then bh_get_quads (or the other way round) leaves the same state and sees the
+ * same cells as two bh_get_quads calls.  bh_render_quads returns BH_E_STATE between bh_step_begin
+ * and bh_step_end.  The view is checked as by bh_render_bodies (same BH_E_INVALID cases and
+ * bh_last_error text; heavy_mass is checked but not used); NULL e or v: BH_E_INVALID.
+ * Integer adds only: two calls, two engines holding the same tree, or a multi-device handle
+ * return identical bytes.  Working buffers are the call's own, allocated on first use and kept
+ * while the view size is unchanged. */
+int bh_render_quads(bh_engine *e, const bh_view *v, uint32_t *lines, int64_t *n_quads);
+
+/* HIP-event duration (ms) of the last bh_render_quads' kernels (cells + the two scans, or the
+ * counting kernel alone when lines was NULL); 0 before the first. */
+int bh_render_quads_kernel_ms(const bh_engine *e, double *ms);
 
 /* Per-phase device timings (ms) of the last bh_step call, summed over its steps:
  * [0] tree build, [1] traversal, [2] integration, [3] merge, [4] all-gather. */
