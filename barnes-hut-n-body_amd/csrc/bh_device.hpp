@@ -131,7 +131,10 @@ __device__ __forceinline__ SpanSlot span_get(const SpanSlot *base, size_t, size_
 // the critical path once the traversal's last workgroups are placed, and at the default priority
 // a traversal wave sharing their SIMD wins half the issue slots (k_merge_replay, one workgroup:
 // 8-24 us alone, 170 us in the traversal's tail).  s_setprio only orders issue between the waves
-// of one SIMD; alone on the GPU it changes nothing.
+// of one SIMD; alone on the GPU it changes nothing.  Measured again with the merge rule and the
+// next build's sort forked out of the traversal's way (the chain starts behind k_emit_com): the
+// build's later kernels still run beside the traversal, and without the priority C3 takes 1.778
+// against 1.756 ms per step (profiles/r08_chain_fork_ab.md).
 #ifndef BH_CHAIN_PRIO
 #define BH_CHAIN_PRIO 1
 #endif
@@ -319,6 +322,13 @@ struct TreeBuffers {
     uint32_t *heavy = nullptr, *heavy_count = nullptr;
     double heavy_thr = 0.0;
     TravCopy tc{};  // (m null: none)
+    // The pipelined step's overlapped chain forks inside the build (engine.cpp
+    // evaluate_pipelined).  fork_ev: recorded on the build's stream right after k_emit_com, when
+    // the sorted state (dst), the heavy list and the traversal's copies are final and only the
+    // spanning passes are left.  late_ev: the stream waits for it before this build's first kernel
+    // that writes what another build's spanning passes still read (super_list, span_list,
+    // span_children) -- the passes before it write sort and key buffers only.
+    hipEvent_t fork_ev = nullptr, late_ev = nullptr;
 };
 
 int cell_table_depth(int J, int64_t n);

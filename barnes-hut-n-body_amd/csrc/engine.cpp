@@ -334,6 +334,11 @@ struct bh_engine {
     uint32_t *cidx_trav = nullptr, *lanes_trav = nullptr, *T_trav = nullptr;
     bool tc_want = false, tc_done = false;  // build_into: the copies above made by k_emit_com
     uint32_t *tc_box = nullptr;             // (and the merge rule's mailbox header cleared)
+    // the overlapped chain's fork inside the second build (TreeBuffers::fork_ev / late_ev):
+    // fork_want is the event a build that makes the copies records after its k_emit_com (forked:
+    // it did), chain_late the one the overlapped build waits for before it writes the span lists
+    hipEvent_t fork_want = nullptr, chain_late = nullptr;
+    bool forked = false;
     int64_t trav_cap = 0;
     bool prebuilt = false;  // the current step's first build was made by the previous step
     // ... by the previous call's last step: that build's error flags are in scalars[10] (they
@@ -921,6 +926,10 @@ int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, b
         tb.tc.T = e->T_trav;
         tb.tc.box_header = e->tc_box;
     }
+    // (a build followed by k_trav_inputs forks after that kernel: it reads what the rule writes)
+    e->forked = e->tc_done && e->fork_want;
+    if (e->forked) tb.fork_ev = e->fork_want;
+    if (overlap) tb.late_ev = e->chain_late;
     tb.keys_ready = e->keys_ready && !overlap;
     e->keys_ready = false;
     if (!overlap) e->mir_fresh = false;  // the jitter may move bodies
@@ -2245,6 +2254,13 @@ int mirror_launch(bh_engine *e, const BodyState &src, hipStream_t after_pos, hip
 
 // The second evaluation of a pipelined step: build, second traversal with the fused kick, and
 // next step's first build; e->prebuilt tells the next evaluation its tree is there.
+// Order on the device:
+//   engine's stream:  build ... k_emit_com | k_span_children, k_com_span (_top) | traversal | join
+//   overlap stream:                        | [removal count] merge rule, next build's sort |
+//                                            ... its k_fixup_cells onwards (after the span
+//                                            passes), [deep: the next a(t)]
+// The host enqueues the chain after the traversal (lastTree's buffer swap lies between the span
+// passes' launch and the overlapped build's); the events alone decide where it runs.
 // last: the call's last step -- this step's tree is lastTree (BHA:435): its walk structures are
 // copied aside before the overlapped build reuses them, and the state before that build's jitter
 // (the previous slot order) becomes the caller-visible `view`.
@@ -2260,9 +2276,10 @@ int mirror_launch(bh_engine *e, const BodyState &src, hipStream_t after_pos, hip
 int evaluate_pipelined(bh_engine *e, bool last) {
     const int64_t n = e->n;
     hipStream_t s = e->stream;
-    // the merge rule's mailbox header is cleared by k_trav_inputs below (after the previous merge
-    // rule, which the engine's stream waited for, and before the overlapped one): a fill of its
-    // own sat on the engine's hardware queue between the build and the traversal
+    // the merge rule's mailbox header is cleared by the build's k_emit_com, or by k_trav_inputs
+    // below (after the previous merge rule, which the engine's stream waited for, and before the
+    // overlapped one, which forks behind whichever of the two ran): a fill of its own sat on the
+    // engine's hardware queue between the build and the traversal
     const bool merging = e->p.merge_min_dist > 0.0 && e->n > 1 && e->heavy_possible;
     if (merging) TRY(merge_bufs(e));
     TRY(mark(e, -1));
@@ -2275,10 +2292,27 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     e->lane_hold = true;
     e->tc_want = BH_TRAV_COPY_IN_BUILD != 0;
     e->tc_box = merging ? reinterpret_cast<uint32_t *>(e->box) : nullptr;
+    // With the mirror on, a call's last step runs the merge rule and the mirror's caller-order
+    // gather of positions and masses before the traversal (~0.15 ms in line): the mirror's 40 MB
+    // cross PCIe from then on instead of from when the overlapped merge rule and gather find wave
+    // slots beside the traversal, ~0.45 ms later (round 4 drop-in trace)
+    const bool early = last && e->mirror_on;
+    // The overlapped chain forks at the end of the build's k_emit_com: the sorted positions, the
+    // heavy list and the traversal's own copies of masses and flags are final there, the mailbox
+    // header is cleared, and only the spanning passes (one workgroup on one CU for most of their
+    // ~50 us) stand between the build and the traversal.  The merge rule and the next build's
+    // sort run in that window on an otherwise idle GPU instead of waiting for wave slots beside
+    // the traversal.  Not when the build leaves the copies to k_trav_inputs (a re-sorted lane
+    // map): that kernel reads the masses and flags the rule writes, so the chain starts after it.
+    e->fork_want = early ? nullptr : e->pipe_ev[2];
+    e->chain_late = nullptr;
     // velocities: permuted by the kick below; the heavy list for the merge rule that follows
     const int rc_b2 = build_into(e, s, false, true, false, merging && BH_HEAVY_CARRY);
     e->lane_hold = false;
     e->tc_want = false;
+    e->fork_want = nullptr;
+    const bool forked = e->forked;
+    e->forked = false;
     TRY(rc_b2);
     TRY(mark(e, 0));
     // with profiling on, the overlapped chain waits for the timing event just recorded after the
@@ -2295,11 +2329,6 @@ int evaluate_pipelined(bh_engine *e, bool last) {
         HIPCHK(e, hipGetLastError());
     }
     e->tc_done = false;
-    // With the mirror on, a call's last step runs the merge rule and the mirror's caller-order
-    // gather of positions and masses before the traversal (~0.15 ms in line): the mirror's 40 MB
-    // cross PCIe from then on instead of from when the overlapped merge rule and gather find wave
-    // slots beside the traversal, ~0.45 ms later (round 4 drop-in trace)
-    const bool early = last && e->mirror_on;
     if (early) {
         copy_u32(e->scalars + 8, e->scalars + 2, s);  // the removals before the last merge rule
         HIPCHK(e, hipGetLastError());
@@ -2316,7 +2345,17 @@ int evaluate_pipelined(bh_engine *e, bool last) {
             e->mid_cv.notify_all();
         }
     }
-    if (built_mark && !early) {
+    if (forked) {
+        // the chain starts behind k_emit_com; from its build's first kernel that writes the span
+        // lists on it waits for this build's spanning passes (the event after the build)
+        HIPCHK(e, hipStreamWaitEvent(e->pipe_stream, e->pipe_ev[2], 0));
+        if (built_mark) {
+            e->chain_late = built_mark;
+        } else {
+            HIPCHK(e, hipEventRecord(e->pipe_ev[0], s));
+            e->chain_late = e->pipe_ev[0];
+        }
+    } else if (built_mark && !early) {
         HIPCHK(e, hipStreamWaitEvent(e->pipe_stream, built_mark, 0));
     } else {
         HIPCHK(e, hipEventRecord(e->pipe_ev[0], s));
@@ -2355,6 +2394,7 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     e->lane_defer = !last;  // (a call ends with a compaction: its last build re-sorts in place)
     const int rc_b1 = build_into(e, e->pipe_stream, true, false, last);  // step s+1's first tree (BHA:359)
     e->lane_defer = false;
+    e->chain_late = nullptr;
     TRY(rc_b1);
     if (deep) {
         // ... and a(t) of step s+1 on it (BHA:407-408): a force evaluation reads positions and

@@ -2368,6 +2368,8 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
         k_morton<<<grid_for(n), TB, 0, s>>>(n, b.src.x, b.src.y, b.src.cidx, g, b.keys, b.keys32,
                                             b.idx);
     size_t bytes = b.scratch_bytes;
+    // (the one-workgroup front writes the cell table, the group list and the sorted state)
+    if (small && b.late_ev && (st = hipStreamWaitEvent(s, b.late_ev, 0)) != hipSuccess) return st;
     if (small) {
         k_small_front<<<1, SF_TB, sizeof(uint64_t) * P, s>>>(
             n, P, !ready, g, D0, b.src, b.dst, b.keys, b.keys32, b.keys32_s, b.perm, b.keys_s,
@@ -2396,6 +2398,9 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
         if (st != hipSuccess) return st;
         k_key_gather<<<grid_for(n), TB, 0, s>>>(n, b.keys, b.perm, b.keys_s);
     }
+    // the sort above wrote keys, permutation and bucket tables only: what follows writes
+    // super_list, then span_list and span_children
+    if (!small && b.late_ev && (st = hipStreamWaitEvent(s, b.late_ev, 0)) != hipSuccess) return st;
     if (small) {
     } else if (BH_FIXUP_CELLS)
         k_fixup_cells<<<grid_for(std::max<int64_t>(n, nbins1)), TB, 0, s>>>(
@@ -2432,6 +2437,10 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
         k_span_find<<<span_grid, TB, 0, s>>>(n, g.J, D0, b.keys_s, b.cpl, b.base, b.cell_start,
                                              b.span_list, b.span_stride, b.super_list, n_groups,
                                              b.nodes);
+    // from here on only nodes, span_children and the lists above are touched
+    // (the event attached to k_emit_com's launch instead, hipExtLaunchKernelGGL's stop event,
+    // costs the build the same ~7 us at C3: not used)
+    if (b.fork_ev && (st = hipEventRecord(b.fork_ev, s)) != hipSuccess) return st;
     k_span_children<<<span_grid, TB, 0, s>>>(g.J, b.span_list, b.span_stride, b.nodes,
                                              b.span_children);
     k_com_span<<<n_groups, SPAN_TB, 0, s>>>(g.J, b.span_list, b.span_stride, b.span_children,
