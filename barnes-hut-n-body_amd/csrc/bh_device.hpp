@@ -135,12 +135,7 @@ __device__ __forceinline__ SpanSlot span_get(const SpanSlot *base, size_t, size_
 // next build's sort forked out of the traversal's way (the chain starts behind k_emit_com): the
 // build's later kernels still run beside the traversal, and without the priority C3 takes 1.778
 // against 1.756 ms per step (profiles/r08_chain_fork_ab.md).
-#ifndef BH_CHAIN_PRIO
-#define BH_CHAIN_PRIO 1
-#endif
-__device__ __forceinline__ void chain_prio() {
-    if (BH_CHAIN_PRIO) asm volatile("s_setprio 3");
-}
+__device__ __forceinline__ void chain_prio() { asm volatile("s_setprio 3"); }
 
 // Workgroup i of a launch runs on XCD i % 8 (8 XCDs, each with its own 4 MB L2).  For gathers
 // whose neighbouring blocks read overlapping lines, xcd_block() remaps the hardware block index
@@ -647,11 +642,6 @@ struct MergePair;
 void copy_trav_inputs(int64_t n, const double *m, double *m_t, const uint32_t *cidx,
                       uint32_t *cidx_t, const uint32_t *lanes, uint32_t *lanes_t,
                       const uint32_t *T, uint32_t *T_t, hipStream_t s, MergePair *box = nullptr);
-// k_kick_drift of a2 written by lane (lanes: lane -> slot, or null) plus, when mf.keys is set, the
-// next build's keys and bucket assignment -- the drifting traversal's epilogue as its own pass
-void kick_drift_keys(int64_t n, const double *a2, double *x, double *y, double *vx, double *vy,
-                     const uint32_t *cidx, double dtHalf, double dt, const uint32_t *lanes,
-                     const Geometry &g, const MortonFuse &mf, hipStream_t s);
 void kick(int64_t n, const double *a2, double *vx, double *vy, double dtHalf, hipStream_t s,
           const uint32_t *lanes = nullptr, GatherLayout gl = GatherLayout{});
 void iota_u32(uint32_t *p, int64_t n, hipStream_t s);
@@ -722,9 +712,6 @@ size_t compact_scratch_bytes(int64_t n);
 hipError_t compact_lanes(int64_t n, const uint32_t *lanes, const uint32_t *keep,
                          const uint32_t *pos, uint32_t *flag, uint32_t *qpos, uint32_t *out,
                          void *tmp, size_t tmp_bytes, hipStream_t s);
-// (flag, qpos of that compact_lanes call) interleaved pairs by lane: out[2 qpos[q]..] = a2[2 q..]
-void compact_lane_pairs(int64_t n, const uint32_t *flag, const uint32_t *qpos, const double *a2,
-                        double *out, hipStream_t s);
 void compact_pair(int64_t n, const uint32_t *keep, const uint32_t *pos, const double *sx,
                   const double *sy, double *dx, double *dy, hipStream_t s);
 hipError_t compact_state(int64_t n, uint32_t *keep, const BodyState &src, const BodyState &dst,

@@ -262,8 +262,6 @@ struct bh_engine {
     bool lane_sort = false;    // BH_LANE_ORDER_SORT=1 at creation: re-sort with the radix sort
     // a due re-sort of the pipelined step's lane map, run beside the next first traversal on its
     // own buffers (lane_refresh_beside) and swapped in before the second build
-    bool lane_defer = false;   // this overlapped build may leave a due re-sort to that
-    bool lane_hold = false;    // this second build leaves a due re-sort to the next overlapped one
     bool lr_pending = false;   // a re-sort is due from the prebuilt tree's keys
     bool lr_ready = false;     // lanes_next holds it once lr_ev completes
     uint32_t *lanes_next = nullptr, *lr_hkey = nullptr, *lr_hkey_s = nullptr, *lr_slot = nullptr;
@@ -332,31 +330,18 @@ struct bh_engine {
     size_t nodes_alt_cap = 0;
     double *m_trav = nullptr;
     uint32_t *cidx_trav = nullptr, *lanes_trav = nullptr, *T_trav = nullptr;
-    bool tc_want = false, tc_done = false;  // build_into: the copies above made by k_emit_com
-    uint32_t *tc_box = nullptr;             // (and the merge rule's mailbox header cleared)
-    // the overlapped chain's fork inside the second build (TreeBuffers::fork_ev / late_ev):
-    // fork_want is the event a build that makes the copies records after its k_emit_com (forked:
-    // it did), chain_late the one the overlapped build waits for before it writes the span lists
-    hipEvent_t fork_want = nullptr, chain_late = nullptr;
-    bool forked = false;
     int64_t trav_cap = 0;
     bool prebuilt = false;  // the current step's first build was made by the previous step
     // ... by the previous call's last step: that build's error flags are in scalars[10] (they
     // belong to the step that uses the tree, the next call's first, which takes them over)
     bool carried_flags = false;
-    // deep pipeline: the previous step also evaluated a(t) on that tree (beside its own second
-    // traversal), by lane of the current map, with these force parameters
-    bool forces_ready = false;
     // the velocities are still in the previous slot order, in alt (the overlapped build's
     // permutation, read by the next step's first kick); null: st holds them
     const uint32_t *vel_perm = nullptr;
-    ForceParams fp_ready{0.0, 0.0, 0.0};
-    double *a2_alt = nullptr;  // a2's compaction target (the carried forces over removals)
-    int64_t a2_alt_cap = 0;
     bool fuse_keys = false;   // the next KICK_DRIFT traversal writes the next build's keys / buckets
     bool keys_ready = false;  // ... and it did: the next full build skips k_morton, k_bucket_count
     hipEvent_t pipe_ev[3] = {nullptr, nullptr, nullptr};
-    hipStream_t pipe_stream = nullptr;  // the overlapped work's stream (BH_PIPE_PRIORITY)
+    hipStream_t pipe_stream = nullptr;  // the overlapped work's stream (the highest priority)
     // A call's last step is pipelined too (the front-end calls bh_step(1) once per frame): the
     // call then ends with the next step's first tree already built (prebuilt: st in its order,
     // jitter applied, nodes).  What the caller sees -- the reference's bodies after step(), before
@@ -441,7 +426,6 @@ struct bh_engine {
     bool profiling = false;
     std::vector<hipEvent_t> ev;
     std::vector<int> ev_phase;
-    std::vector<int> ev_weight;  // traversal intervals: evaluations they contain
     size_t ev_used = 0;
     double phase_ms[kPhases] = {0, 0, 0, 0, 0};
     double trav_ms_sum = 0.0;
@@ -795,8 +779,7 @@ TreeBuffers tree_buffers(bh_engine *e) {
 }
 
 // ---- profiling events ----------------------------------------------------------------
-// weight: force evaluations inside a traversal interval (the deep pipeline's holds two)
-int mark(bh_engine *e, int phase, int weight = 1) {  // close the interval of `phase` begun at the last mark
+int mark(bh_engine *e, int phase) {  // close the interval of `phase` begun at the last mark
     if (!e->profiling) return BH_OK;
     // phases are contiguous on the stream: the previous phase's end mark starts the next one
     if (phase < 0 && e->ev_used > 0) return BH_OK;
@@ -810,11 +793,9 @@ int mark(bh_engine *e, int phase, int weight = 1) {  // close the interval of `p
         }
         e->ev.push_back(ev);
         e->ev_phase.push_back(-1);
-        e->ev_weight.push_back(1);
     }
     HIPCHK(e, hipEventRecord(e->ev[e->ev_used], e->stream));
     e->ev_phase[e->ev_used] = phase;  // phase of the interval ending here (-1: start marker)
-    e->ev_weight[e->ev_used] = weight;
     ++e->ev_used;
     e->timings_pending = true;
     return BH_OK;
@@ -833,27 +814,20 @@ int collect_timings(bh_engine *e) {
         float ms = 0.f;
         HIPCHK(e, hipEventElapsedTime(&ms, e->ev[i - 1], e->ev[i]));
         e->phase_ms[ph] += ms;
-        if (ph == 1) {  // per evaluation: an interval holding w evaluations counts w times
-            const int w = e->ev_weight[i];
+        if (ph == 1) {  // per evaluation
             e->trav_ms_sum += ms;
-            e->trav_launches += w;
-            for (int j = 0; j < w; ++j) e->trav_samples.push_back(ms / w);
+            ++e->trav_launches;
+            e->trav_samples.push_back(ms);
         }
     }
     e->timings_pending = false;
     return BH_OK;
 }
 
-// The pipelined step's first traversal also computes the second build's Morton keys and
-// bucket counts (KICK_DRIFT epilogue, bh_device.hpp MortonFuse).
-#ifndef BH_FUSE_KEYS
-#define BH_FUSE_KEYS 1
-#endif
-
 // ---- buildTree() (BHA:359-366): sort + build; the state moves to the new Morton order ----
 #ifndef BH_LANE_REFRESH
 // builds between Hilbert re-sorts of the lane map (0: Morton lanes).  With the re-sort beside the
-// first traversal (BH_LANE_DEFER) a fresher map pays: C3 1.84-1.85 ms per step at 16, 1.82-1.83 at
+// first traversal (lane_refresh_beside) a fresher map pays: C3 1.84-1.85 ms per step at 16, 1.82-1.83 at
 // 8, 1.814-1.820 at 6, 1.82-1.83 at 4 (round 4, profiles/r04L2_lane_refresh_ab.txt) -- with the
 // radix sort, ~0.76 ms of kernels per re-sort.  The run scatter (tree_build.hip lane_order_into)
 // takes ~0.06 ms beside the traversal: means of 6 interleaved runs 1.7122 at 6, 1.7079 at 3,
@@ -864,35 +838,49 @@ int collect_timings(bh_engine *e) {
 #ifndef BH_LANE_REFRESH_SHARDED
 #define BH_LANE_REFRESH_SHARDED 16  // multi-rank engines (no pipelined step: the re-sort is in line)
 #endif
-#ifndef BH_LANE_DEFER
-#define BH_LANE_DEFER 1  // pipelined steps re-sort beside the first traversal (lane_refresh_beside)
-#endif
 // "theta is zero" is a statement about theta^2, the value the criterion uses (BHA:226-228) and
 // the one evaluate() picks the all-pairs kernel by: for 0 < |theta| < ~1.5e-162 the square
 // underflows to zero.  Everything that prepares for a tree walk (lane maps, pipelining, LET
 // builds, the snapshot) asks this, so that it never disagrees with the kernel choice.
 bool theta2_is_zero(const bh_engine *e) { return e->p.theta * e->p.theta == 0.0; }
 
-// overlap: the pipelined step's build on stream `s` -- into nodes_alt and alt without the
-// velocities (permute_velocities follows) and without the final swap (the caller swaps)
-// overlap: the pipelined step's next tree, built beside the second traversal into nodes_alt /
-// alt with its own permutation (perm2; the traversal reads perm), velocities left to
-// permute_velocities.  keep_v: the velocities stay in the previous slot order (in alt after the
-// swap) for a traversal that permutes them as it kicks (KickArgs::perm).
-// carry: a call's last overlapped build, whose tree the next call uses -- its error flags go to
-// scalars[10] instead of the running call's scalars[1] (evaluate / bh_get_quads take them over)
-#ifndef BH_HEAVY_CARRY
-#define BH_HEAVY_CARRY 1  // the pipelined step's second build lists the heavy bodies (k_prep)
-#endif
-// heavy_list: k_prep lists the merge rule's heavy bodies in this build's order (the rule follows
-// the build before any other build: masses change only in the rule, BHA:518)
-int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, bool carry = false,
-               bool heavy_list = false) {
+// What one build is asked for (build_into), and what it did.
+struct BuildRequest {
+    // the pipelined step's next tree, built on stream `s` beside the second traversal into
+    // nodes_alt / alt with its own permutation (perm2; the traversal reads perm), velocities left
+    // to permute_velocities, and without the final swap (the caller swaps)
+    bool overlap;
+    // the velocities stay in the previous slot order (in alt after the swap) for a traversal that
+    // permutes them as it kicks (KickArgs::perm)
+    bool keep_v;
+    // a call's last overlapped build, whose tree the next call uses -- its error flags go to
+    // scalars[10] instead of the running call's scalars[1] (evaluate / bh_get_quads take them over)
+    bool carry;
+    // k_prep lists the merge rule's heavy bodies in this build's order (the rule follows the
+    // build before any other build: masses change only in the rule, BHA:518)
+    bool heavy_list;
+    // a due re-sort of the lane map is left to lane_refresh_beside: by the second build
+    // (lane_hold, to the next overlapped one) and by an overlapped build that may (lane_defer)
+    bool lane_hold, lane_defer;
+    // the second traversal's input copies (m_trav ...) made by k_emit_com, which also clears the
+    // merge rule's mailbox header tc_box
+    bool tc_want;
+    uint32_t *tc_box;
+    // the overlapped chain's fork inside the second build (TreeBuffers::fork_ev / late_ev): the
+    // event a build that makes the copies records after its k_emit_com, and the one an overlapped
+    // build waits for before it writes the span lists
+    hipEvent_t fork_want, chain_late;
+    // out: the build made the copies; it recorded fork_want
+    bool tc_done, forked;
+};
+
+int build_into(bh_engine *e, hipStream_t s, BuildRequest &rq) {
+    const bool overlap = rq.overlap;
     const int64_t n = e->n;
     TreeBuffers tb = tree_buffers(e);
-    if (heavy_list && e->heavy_dirty)  // (a list no rule consumed: a call that failed between)
+    if (rq.heavy_list && e->heavy_dirty)  // (a list no rule consumed: a call that failed between)
         HIPCHK(e, hipMemsetAsync(e->scalars + 14, 0, sizeof(uint32_t), s));
-    e->heavy_ready = heavy_list && n > 0;
+    e->heavy_ready = rq.heavy_list && n > 0;
     if (e->heavy_ready) {
         e->heavy_dirty = true;
         tb.heavy = e->heavy;
@@ -904,8 +892,8 @@ int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, b
         tb.nodes = e->nodes_alt;
         tb.perm = e->perm2;
     }
-    if (carry) tb.scalars = e->scalars + 9;  // (the build writes scalars[1] of its buffers)
-    if (keep_v) tb.src.vx = tb.src.vy = nullptr;
+    if (rq.carry) tb.scalars = e->scalars + 9;  // (the build writes scalars[1] of its buffers)
+    if (rq.keep_v) tb.src.vx = tb.src.vy = nullptr;
     // Hilbert waves (every rank alike): re-sorted every BH_LANE_REFRESH builds, carried through
     // the build's permutation by k_emit_com in between
     const bool use_lanes = BH_LANE_REFRESH > 0 && n > 0 && !theta2_is_zero(e);
@@ -913,23 +901,23 @@ int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, b
     const bool due = use_lanes && e->lanes_valid && e->lanes_age >= every;
     // (pipelined steps: the re-sort is left to the next first traversal's side, see
     // lane_refresh_beside; the map is carried through this build meanwhile)
-    const bool defer = due && BH_LANE_DEFER && ((overlap && e->lane_defer) || e->lane_hold);
+    const bool defer = due && ((overlap && rq.lane_defer) || rq.lane_hold);
     const bool refresh = use_lanes && (!e->lanes_valid || (due && !defer));
     tb.lanes_remap = use_lanes && !refresh ? e->lanes : nullptr;
     // the second traversal's copies made by the build (k_emit_com) instead of k_trav_inputs --
     // not when the map is re-sorted after the build (lane_order rewrites it)
-    e->tc_done = e->tc_want && n > 0 && !refresh;
-    if (e->tc_done) {
+    rq.tc_done = rq.tc_want && n > 0 && !refresh;
+    if (rq.tc_done) {
         tb.tc.m = e->m_trav;
         tb.tc.cidx = e->cidx_trav;
         tb.tc.lanes = tb.lanes_remap ? e->lanes_trav : nullptr;
         tb.tc.T = e->T_trav;
-        tb.tc.box_header = e->tc_box;
+        tb.tc.box_header = rq.tc_box;
     }
     // (a build followed by k_trav_inputs forks after that kernel: it reads what the rule writes)
-    e->forked = e->tc_done && e->fork_want;
-    if (e->forked) tb.fork_ev = e->fork_want;
-    if (overlap) tb.late_ev = e->chain_late;
+    rq.forked = rq.tc_done && rq.fork_want;
+    if (rq.forked) tb.fork_ev = rq.fork_want;
+    if (overlap) tb.late_ev = rq.chain_late;
     tb.keys_ready = e->keys_ready && !overlap;
     e->keys_ready = false;
     if (!overlap) e->mir_fresh = false;  // the jitter may move bodies
@@ -975,9 +963,6 @@ int build_into(bh_engine *e, hipStream_t s, bool overlap, bool keep_v = false, b
 // The velocities left in the previous slot order by a pipelined step (vel_perm) -> st, for any
 // reader other than the next step's first kick (materialize_positions calls it: every reader of
 // the replica outside the step does that first).
-#ifndef BH_FOLD_VEL_PERM
-#define BH_FOLD_VEL_PERM 1
-#endif
 int materialize_velocities(bh_engine *e) {
     if (!e->vel_perm) return BH_OK;
     permute_velocities(e->n, e->vel_perm, e->alt.vx, e->alt.vy, e->st.vx, e->st.vy, e->stream);
@@ -988,7 +973,8 @@ int materialize_velocities(bh_engine *e) {
 
 int build(bh_engine *e) {
     TRY(materialize_velocities(e));
-    return build_into(e, e->stream, false);
+    BuildRequest rq{};  // in place, on the engine's stream, nothing carried or left to others
+    return build_into(e, e->stream, rq);
 }
 
 // theta = 0 workspace: flags per node slot, selected indices and the leaf list per body.
@@ -1039,18 +1025,12 @@ int drop_carried_flags(bh_engine *e) {
 // are disjoint, so the concurrent writes never overlap.
 // kick (one GPU, tree walk): the following KDK update is fused into the traversal's epilogue
 // and *fused is set; otherwise the caller runs the integration kernel on a2.
-#ifndef BH_FUSE_KICK
-#define BH_FUSE_KICK 1
-#endif
 #ifndef BH_ROUND_WEIGHTS
 #define BH_ROUND_WEIGHTS 1, 1, 1, 1  // relative sizes of a rank's rounds (BH_ROUND_FRACS)
 #endif
 
 // ---- multi-rank: the build as a locally essential tree (let.hip) ----------------------
 int pinned_reserve(bh_engine *e, size_t bytes);
-#ifndef BH_LET_FUSE_KEYS
-#define BH_LET_FUSE_KEYS 1  // the subset gather writes the LET build's keys and buckets
-#endif
 #ifndef BH_LET_REFRESH
 #define BH_LET_REFRESH 32  // LET builds between full builds (the replicated Morton order)
 #endif
@@ -1176,9 +1156,6 @@ TreeBuffers let_tree_buffers(bh_engine *e) {
 inline int64_t let_capacity(int64_t known) {
     return known + (known >> BH_LET_HEADROOM_SHIFT) + 4096;
 }
-#ifndef BH_SPL_EXTEND
-#define BH_SPL_EXTEND 1
-#endif
 #ifndef BH_LET_MIN_WORLD
 #define BH_LET_MIN_WORLD 2
 #endif
@@ -1395,14 +1372,14 @@ int evaluate_let(bh_engine *e, KickMode kick, bool *done) {
         // with rocprim and sizes the subset afterwards)
         // a grown capacity S: splitters for its new padding tail (else one bucket takes it all
         // and sorts it alone: up to 1 ms per build while the call's largest subset still grows)
-        if (BH_SPL_EXTEND && e->s_spl_nb > 0 && S <= e->let_sub_cap && e->geo.J == e->let_J &&
+        if (e->s_spl_nb > 0 && S <= e->let_sub_cap && e->geo.J == e->let_J &&
             sort_buckets(S) > e->s_spl_nb) {
             extend_splitters(e->s_spl, e->s_spl_nb, sort_buckets(S), e->geo.J, e->stream);
             HIPCHK(e, hipGetLastError());
             e->s_spl_nb = sort_buckets(S);
         }
         MortonFuse mf{};
-        const bool fuse = BH_LET_FUSE_KEYS && e->let_known > 0 && e->s_spl_nb > 0 &&
+        const bool fuse = e->let_known > 0 && e->s_spl_nb > 0 &&
                           S <= e->let_sub_cap && e->geo.J == e->let_J && e->s_keys;
         if (fuse)
             mf = MortonFuse{e->s_keys, e->s_keys32, e->s_spl, e->s_spl_nb, e->s_cnt, e->s_base,
@@ -1581,13 +1558,11 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
     }
     e->let_age = 0;
     const int64_t n = e->n;
-    bool have_forces = false;  // a(t) on this tree, evaluated ahead by the previous step
     if (e->prebuilt) {  // the pipelined step built this tree (single GPU: nothing deferred)
         e->prebuilt = false;
         TRY(take_carried_flags(e));
         e->view_pending = false;  // its jitter is now part of the state (BHA:146-151)
         e->mir_fresh = false;
-        have_forces = e->forces_ready;
     } else {
         TRY(materialize_positions(e));  // the replica's x, y; a2 is free again
         TRY(sync_velocities(e));        // before the full build permutes the state
@@ -1605,10 +1580,7 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
         }
         TRY(mark(e, 0));
     }
-    e->forces_ready = false;
     ForceParams fp{e->p.G, e->p.soft2, e->p.theta * e->p.theta};  // BHA:378
-    have_forces = have_forces && fp.G == e->fp_ready.G && fp.soft2 == e->fp_ready.soft2 &&
-                  fp.theta2 == e->fp_ready.theta2;
     const uint32_t *d_T = e->base + n;
     if (pot) {  // the potential on this tree, by this engine alone, over the whole list
         if (!pot->run) return BH_OK;
@@ -1651,9 +1623,9 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
                      a2, vis ? &counters : nullptr, fs, nullptr, lanes);
     };
     if ((!e->comm && !e->group && !e->solo) || visits) {
-        if (BH_FUSE_KICK && kick != KICK_NONE && !direct && !visits && fused) {
+        if (kick != KICK_NONE && !direct && !visits && fused) {
             KickArgs ka{kick, e->st.vx, e->st.vy, e->p.dt * 0.5, e->p.dt};
-            if (e->vel_perm && kick == KICK_DRIFT && !have_forces) {  // v[p] = old v[perm[p]]
+            if (e->vel_perm && kick == KICK_DRIFT) {  // v[p] = old v[perm[p]]
                 ka.svx = e->alt.vx;
                 ka.svy = e->alt.vy;
                 ka.perm = e->vel_perm;
@@ -1663,23 +1635,13 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
             // (not into a breadth-first walk: one body per wave would make one bucket-count
             // atomic per body -- C1 'R' 37.6 against 21.2 us for the kick-only walk --, the build's
             // k_morton_count aggregates them per wave)
-            if (BH_FUSE_KEYS && e->fuse_keys && kick == KICK_DRIFT && e->spl_nb > 0 && n > 0 &&
+            if (e->fuse_keys && kick == KICK_DRIFT && e->spl_nb > 0 && n > 0 &&
                 !traverse_is_bfs(e->node_cap, 0, n, KICK_DRIFT, false)) {
                 ka.mf = MortonFuse{e->keys, e->keys32, e->spl, e->spl_nb, e->cnt, e->base,
                                    e->bcount};
                 e->keys_ready = true;
             }
             e->fuse_keys = false;
-            if (have_forces && kick == KICK_DRIFT) {
-                // a(t) is in a2 by lane (the previous step's deep pipeline): the epilogue alone
-                TRY(mark(e, -1));
-                kick_drift_keys(n, e->a2, e->st.x, e->st.y, e->st.vx, e->st.vy, e->st.cidx,
-                                ka.dtHalf, ka.dt, lanes, e->geo, ka.mf, e->stream);
-                HIPCHK(e, hipGetLastError());
-                *fused = true;
-                TRY(mark(e, 2));
-                return BH_OK;
-            }
             WaveOrder wo;
             TRY(wave_order_for(e, 0, n, e->stream, wo));
             traverse(e->nodes, e->node_cap, d_T, e->st.x, e->st.y, e->st.m, e->st.cidx, 0, n, e->geo, fp,
@@ -1871,18 +1833,6 @@ int finish_merges(bh_engine *e, uint32_t *overflow, uint32_t *tree_flags = nullp
                                 e->scratch, e->scratch_bytes, e->stream));
         std::swap(e->lanes, e->keys32_s);
         e->inv_valid = false;
-        if (e->prebuilt && e->forces_ready) {
-            // the next step's a(t), already evaluated by lane, follows its lanes (flag, qpos)
-            if (e->a2_alt_cap < e->cap) {
-                TRY(dev_alloc(e, e->a2_alt, 2 * (size_t)e->cap));
-                e->a2_alt_cap = e->cap;
-            }
-            compact_lane_pairs(n, e->idx, e->keys32, e->a2, e->a2_alt, e->stream);
-            HIPCHK(e, hipGetLastError());
-            std::swap(e->a2, e->a2_alt);  // (one GPU: both hold 2 cap doubles)
-        }
-    } else {
-        e->forces_ready = false;
     }
     e->n = n - (int64_t)nd;
     e->inv_valid = false;  // another n: another exchange layout
@@ -2023,34 +1973,13 @@ int agree_let_flags(bh_engine *e, uint32_t ls[2], uint32_t *own_sub) {
 // The traversal reads copies of what they overwrite (masses, flags, lane map, node count) and
 // the build writes the other node array; the velocities follow the build's permutation once
 // the kick is done.  Every kernel sees the inputs of the sequential order: bit-identical.
-#ifndef BH_PIPELINE
-#define BH_PIPELINE 1
-#endif
-#ifndef BH_PIPE_PRIORITY
-#define BH_PIPE_PRIORITY 1  // the overlapped work's stream at the highest priority
-#endif
-// The deep pipeline: the next step's a(t) evaluated beside this step's second traversal (kick +
-// drift + keys as their own pass) -- for body lists up to BH_DEEP_PIPE_MAX_N.  Measured slower at
-// C3 (1.925 against 1.884 ms per step, round 4): the next tree is ready only after the
-// traversal's last waves are placed, so the two evaluations barely overlap and share the caches
-// when they do.  A small list leaves most of the GPU idle in each traversal (a few hundred waves
-// on 1 024 SIMDs), so there the two evaluations run side by side (round 6).
-#ifndef BH_DEEP_PIPE_MAX_N
-#define BH_DEEP_PIPE_MAX_N 0
-#endif
-int64_t deep_pipe_max_n() {
-    static const int64_t v = [] {
-        const char *t = std::getenv("BH_DEEP_PIPE_MAX_N");
-        return t ? (int64_t)std::atoll(t) : (int64_t)BH_DEEP_PIPE_MAX_N;
-    }();
-    return v;
-}
-#ifndef BH_PIPE_LAST
-#define BH_PIPE_LAST 1  // pipeline a call's last step too (the next call starts on its tree)
-#endif
-bool pipelined(const bh_engine *e, bool last) {
-    return BH_PIPELINE && BH_FUSE_KICK && (!last || BH_PIPE_LAST) && e->n > 0 && !e->comm &&
-           !e->group && !e->solo && !theta2_is_zero(e);
+// The pipeline stops at the next build: the next step's a(t) evaluated beside this step's second
+// traversal as well was measured slower at C3 (1.925 against 1.884 ms per step, round 4,
+// DESIGN.md) -- the next tree is ready only after the traversal's last waves are placed, so the
+// two evaluations barely overlap and share the caches when they do.
+// A call's last step is pipelined too (the next call starts on its tree).
+bool pipelined(const bh_engine *e) {
+    return e->n > 0 && !e->comm && !e->group && !e->solo && !theta2_is_zero(e);
 }
 
 // The overlap and mirror streams of a one-GPU engine.  HIP hands a process's streams its few
@@ -2061,24 +1990,17 @@ bool pipelined(const bh_engine *e, bool last) {
 // ms).  An engine that never enables the mirror holds two queues, not three.
 // The exchange stream (RCCL all-gathers, or the in-process copies) at the high priority: its
 // few workgroups are dispatched ahead of the traversal rounds' queued ones as soon as a slot
-// frees, instead of in the last round's tail (BH_COMM_PRIORITY=0: the default priority)
-#ifndef BH_COMM_PRIORITY
-#define BH_COMM_PRIORITY 1
-#endif
+// frees, instead of in the last round's tail
 hipError_t comm_stream_create(hipStream_t *s) {
     int lo = 0, hi = 0;
     hipError_t rc = hipDeviceGetStreamPriorityRange(&lo, &hi);
     if (rc != hipSuccess) return rc;
-    return hipStreamCreateWithPriority(s, hipStreamNonBlocking, BH_COMM_PRIORITY ? hi : lo);
+    return hipStreamCreateWithPriority(s, hipStreamNonBlocking, hi);
 }
 
 // The pipelined step's cross-stream events order work on this device only: no system-scope fence
 // when they are recorded (the default one writes back and invalidates the caches for the host)
-#ifndef BH_PIPE_EV_NOFENCE
-#define BH_PIPE_EV_NOFENCE 1
-#endif
-constexpr unsigned kPipeEvFlags =
-    hipEventDisableTiming | (BH_PIPE_EV_NOFENCE ? hipEventDisableSystemFence : 0u);
+constexpr unsigned kPipeEvFlags = hipEventDisableTiming | hipEventDisableSystemFence;
 int pipe_streams(bh_engine *e) {
     for (hipEvent_t &ev : e->pipe_ev)
         if (!ev) HIPCHK(e, hipEventCreateWithFlags(&ev, kPipeEvFlags));
@@ -2087,8 +2009,7 @@ int pipe_streams(bh_engine *e) {
         // priority the overlapped kernels would be dispatched only in its tail
         int lo = 0, hi = 0;
         HIPCHK(e, hipDeviceGetStreamPriorityRange(&lo, &hi));
-        HIPCHK(e, hipStreamCreateWithPriority(&e->pipe_stream, hipStreamNonBlocking,
-                                              BH_PIPE_PRIORITY ? hi : lo));
+        HIPCHK(e, hipStreamCreateWithPriority(&e->pipe_stream, hipStreamNonBlocking, hi));
     }
     return BH_OK;
 }
@@ -2258,21 +2179,12 @@ int mirror_launch(bh_engine *e, const BodyState &src, hipStream_t after_pos, hip
 //   engine's stream:  build ... k_emit_com | k_span_children, k_com_span (_top) | traversal | join
 //   overlap stream:                        | [removal count] merge rule, next build's sort |
 //                                            ... its k_fixup_cells onwards (after the span
-//                                            passes), [deep: the next a(t)]
+//                                            passes)
 // The host enqueues the chain after the traversal (lastTree's buffer swap lies between the span
 // passes' launch and the overlapped build's); the events alone decide where it runs.
 // last: the call's last step -- this step's tree is lastTree (BHA:435): its walk structures are
 // copied aside before the overlapped build reuses them, and the state before that build's jitter
 // (the previous slot order) becomes the caller-visible `view`.
-
-// The second traversal's input copies (masses, flags, lane map, node count) written by the
-// second build's k_emit_com instead of a k_trav_inputs launch between the build and the traversal.
-#ifndef BH_TRAV_COPY_IN_BUILD
-#define BH_TRAV_COPY_IN_BUILD 1
-#endif
-#ifndef BH_PIPE_REUSE_MARK
-#define BH_PIPE_REUSE_MARK 1
-#endif
 int evaluate_pipelined(bh_engine *e, bool last) {
     const int64_t n = e->n;
     hipStream_t s = e->stream;
@@ -2289,9 +2201,14 @@ int evaluate_pipelined(bh_engine *e, bool last) {
         e->lr_ready = false;
         e->lanes_age = 0;
     }
-    e->lane_hold = true;
-    e->tc_want = BH_TRAV_COPY_IN_BUILD != 0;
-    e->tc_box = merging ? reinterpret_cast<uint32_t *>(e->box) : nullptr;
+    BuildRequest b2{};        // the second build: in place on the engine's stream
+    b2.keep_v = true;         // velocities: permuted by the kick below
+    b2.heavy_list = merging;  // for the merge rule that follows
+    b2.lane_hold = true;      // a due lane re-sort waits for the next first traversal's side
+    // the second traversal's input copies (masses, flags, lane map, node count) written by this
+    // build's k_emit_com instead of a k_trav_inputs launch between the build and the traversal
+    b2.tc_want = true;
+    b2.tc_box = merging ? reinterpret_cast<uint32_t *>(e->box) : nullptr;
     // With the mirror on, a call's last step runs the merge rule and the mirror's caller-order
     // gather of positions and masses before the traversal (~0.15 ms in line): the mirror's 40 MB
     // cross PCIe from then on instead of from when the overlapped merge rule and gather find wave
@@ -2304,31 +2221,21 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     // sort run in that window on an otherwise idle GPU instead of waiting for wave slots beside
     // the traversal.  Not when the build leaves the copies to k_trav_inputs (a re-sorted lane
     // map): that kernel reads the masses and flags the rule writes, so the chain starts after it.
-    e->fork_want = early ? nullptr : e->pipe_ev[2];
-    e->chain_late = nullptr;
-    // velocities: permuted by the kick below; the heavy list for the merge rule that follows
-    const int rc_b2 = build_into(e, s, false, true, false, merging && BH_HEAVY_CARRY);
-    e->lane_hold = false;
-    e->tc_want = false;
-    e->fork_want = nullptr;
-    const bool forked = e->forked;
-    e->forked = false;
-    TRY(rc_b2);
+    b2.fork_want = early ? nullptr : e->pipe_ev[2];
+    TRY(build_into(e, s, b2));
     TRY(mark(e, 0));
     // with profiling on, the overlapped chain waits for the timing event just recorded after the
     // build (when nothing else follows the build on this stream): each event recorded on the
     // stream holds the next kernel back by a few microseconds
-    const hipEvent_t built_mark = e->profiling && e->ev_used > 0 && e->tc_done && BH_PIPE_REUSE_MARK
-                                      ? e->ev[e->ev_used - 1]
-                                      : nullptr;
+    const hipEvent_t built_mark =
+        e->profiling && e->ev_used > 0 && b2.tc_done ? e->ev[e->ev_used - 1] : nullptr;
     const bool lanes = e->lanes_valid;
-    if (!e->tc_done) {  // (the build made them otherwise)
+    if (!b2.tc_done) {  // (the build made them otherwise)
         copy_trav_inputs(n, e->st.m, e->m_trav, e->st.cidx, e->cidx_trav,
                          lanes ? e->lanes : nullptr, e->lanes_trav, e->base + n, e->T_trav, s,
                          merging ? e->box : nullptr);
         HIPCHK(e, hipGetLastError());
     }
-    e->tc_done = false;
     if (early) {
         copy_u32(e->scalars + 8, e->scalars + 2, s);  // the removals before the last merge rule
         HIPCHK(e, hipGetLastError());
@@ -2345,15 +2252,19 @@ int evaluate_pipelined(bh_engine *e, bool last) {
             e->mid_cv.notify_all();
         }
     }
-    if (forked) {
+    BuildRequest b1{};  // step s+1's first tree (BHA:359), beside the traversal
+    b1.overlap = true;
+    b1.carry = last;
+    b1.lane_defer = !last;  // (a call ends with a compaction: its last build re-sorts in place)
+    if (b2.forked) {
         // the chain starts behind k_emit_com; from its build's first kernel that writes the span
         // lists on it waits for this build's spanning passes (the event after the build)
         HIPCHK(e, hipStreamWaitEvent(e->pipe_stream, e->pipe_ev[2], 0));
         if (built_mark) {
-            e->chain_late = built_mark;
+            b1.chain_late = built_mark;
         } else {
             HIPCHK(e, hipEventRecord(e->pipe_ev[0], s));
-            e->chain_late = e->pipe_ev[0];
+            b1.chain_late = e->pipe_ev[0];
         }
     } else if (built_mark && !early) {
         HIPCHK(e, hipStreamWaitEvent(e->pipe_stream, built_mark, 0));
@@ -2373,8 +2284,7 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     traverse(e->nodes, e->node_cap, e->T_trav, e->st.x, e->st.y, e->m_trav, e->cidx_trav, 0, n,
              e->geo, fp, e->a2, nullptr, s, &ka, lanes ? e->lanes_trav : nullptr, &wo);
     HIPCHK(e, hipGetLastError());
-    const bool deep = deep_pipe_max_n() > 0 && e->n <= deep_pipe_max_n();
-    if (!deep) TRY(mark(e, 1));
+    TRY(mark(e, 1));
     TRY(wave_order_next(e, 0, n, s));
     if (last) {
         hipStream_t ps = e->pipe_stream;
@@ -2391,24 +2301,10 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     }
     if (!early) TRY(merge(e, e->pipe_stream, merging));  // BHA:438
     if (early) TRY(mirror_vel(e, e->st, s));  // the velocities once the kick is done
-    e->lane_defer = !last;  // (a call ends with a compaction: its last build re-sorts in place)
-    const int rc_b1 = build_into(e, e->pipe_stream, true, false, last);  // step s+1's first tree (BHA:359)
-    e->lane_defer = false;
-    e->chain_late = nullptr;
-    TRY(rc_b1);
-    if (deep) {
-        // ... and a(t) of step s+1 on it (BHA:407-408): a force evaluation reads positions and
-        // masses only, so it runs beside this traversal, whose tail it fills; the next step's
-        // kick and drift need this traversal's velocities and run after both (kick_drift_keys)
-        traverse(e->nodes_alt, e->nodes_alt_cap, e->base + n, e->alt.x, e->alt.y, e->alt.m,
-                 e->alt.cidx, 0, n, e->geo, fp, e->a2, nullptr, e->pipe_stream, nullptr,
-                 e->lanes_valid ? e->lanes : nullptr, nullptr);
-        HIPCHK(e, hipGetLastError());
-    }
+    TRY(build_into(e, e->pipe_stream, b1));
     HIPCHK(e, hipEventRecord(e->pipe_ev[1], e->pipe_stream));
     HIPCHK(e, hipStreamWaitEvent(s, e->pipe_ev[1], 0));
-    if (deep) TRY(mark(e, 1, 2));  // this traversal, the overlapped chain, the next a(t)
-    if (!last && !deep && BH_FOLD_VEL_PERM) {
+    if (!last) {
         e->vel_perm = e->perm2;  // the next step's first kick reads them through the permutation
     } else {
         permute_velocities(n, e->perm2, e->st.vx, e->st.vy, e->alt.vx, e->alt.vy, s);
@@ -2420,8 +2316,6 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     std::swap(e->node_cap, e->nodes_alt_cap);
     e->prebuilt = true;
     e->carried_flags = last;
-    e->forces_ready = deep;
-    e->fp_ready = fp;
     if (last) {  // the previous order's state (kicked, merged, not yet jittered) is what the caller sees
         std::swap(e->view, e->alt);
         e->view_pending = true;
@@ -2430,9 +2324,6 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     return BH_OK;
 }
 
-#ifndef BH_LAZY_LASTTREE
-#define BH_LAZY_LASTTREE 1
-#endif
 // The positions the call's last build starts from (its jitter moves some of them): kept for the
 // lazy lastTree of bh_get_quads (16 B per body, device copies).
 int snapshot_positions(bh_engine *e) {
@@ -2492,7 +2383,7 @@ int lane_refresh_beside(bh_engine *e) {
 int step_once(bh_engine *e, bool last) {
     const int64_t n = e->n;
     const double dtHalf = e->p.dt * 0.5;  // BHA:412
-    if (pipelined(e, last)) {
+    if (pipelined(e)) {
         TRY(pipe_alloc(e, last));
         if (e->lr_pending && e->prebuilt) TRY(lane_refresh_beside(e));
         e->lr_pending = false;
@@ -2525,7 +2416,7 @@ int step_once(bh_engine *e, bool last) {
         // the call's last build: a full tree for getTreeForDebug (lastTree, BHA:435) -- or, on a
         // multi-rank engine, a LET build like the others, its input positions kept for a lazy
         // full build in bh_get_quads
-        const bool lazy = last && BH_LAZY_LASTTREE && (e->comm || e->group || e->solo);
+        const bool lazy = last && (e->comm || e->group || e->solo);
         if (lazy) TRY(snapshot_positions(e));
         bool let2 = false;
         TRY(evaluate(e, nullptr, KICK_ONLY, &fused, !last || lazy, &let2));  // a(t+dt)
@@ -3172,7 +3063,7 @@ void bh_destroy(bh_engine *e) {
                     e->leaf_flags, e->leaf_sel, e->leaf_count, e->leaf_cover, e->leaves.rec,
                     e->leaf_tmp, e->spl, e->bcount, e->bstart, e->nodes_alt, e->wave_cost, e->run_order,
                     e->m_trav, e->cidx_trav, e->lanes_trav, e->T_trav, e->solo_xchg,
-                    e->lt_x, e->lt_y, e->a2_alt, e->lt_keys, e->lt_cpl, e->lt_base, e->mir_stage,
+                    e->lt_x, e->lt_y, e->lt_keys, e->lt_cpl, e->lt_base, e->mir_stage,
                     e->mir_keep, e->mir_pos, e->mir_tmp, e->mir_idx_stage, e->lanes_next, e->lr_hkey, e->lr_hkey_s,
                     e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,

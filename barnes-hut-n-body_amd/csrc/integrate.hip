@@ -37,42 +37,6 @@ __global__ __launch_bounds__(TB) void k_kick_drift(int64_t n, const double *__re
     if (vmax) wave_vmax(vmax, vxi, vyi);  // (multi-rank: the LET selection's displacement bound)
 }
 
-// The same kick + drift by lane of the traversal's lane map, after an evaluation that was made
-// ahead (the deep pipeline, engine.cpp evaluate_pipelined), with the next build's first two passes
-// (k_morton, k_bucket_count) for the moved body -- what the drifting traversal's epilogue does
-// (traverse.hip trav_wave), operation for operation.
-__global__ __launch_bounds__(TB) void k_kick_drift_keys(int64_t n, const double *__restrict__ a2,
-                                                        double *__restrict__ x,
-                                                        double *__restrict__ y,
-                                                        double *__restrict__ vx,
-                                                        double *__restrict__ vy,
-                                                        const uint32_t *__restrict__ cidx,
-                                                        double dtHalf, double dt,
-                                                        const uint32_t *__restrict__ lanes,
-                                                        Geometry g, MortonFuse mf) {
-    const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
-    if (i >= n) return;
-    const double2_t a = *reinterpret_cast<const double2_t *>(a2 + 2 * i);
-    const int64_t p = lanes ? (int64_t)lanes[i] : i;
-    const double vxi = vx[p] + a.x * dtHalf;
-    const double vyi = vy[p] + a.y * dtHalf;
-    vx[p] = vxi;
-    vy[p] = vyi;
-    const double nx = x[p] + vxi * dt, ny = y[p] + vyi * dt;
-    x[p] = nx;
-    y[p] = ny;
-    if (mf.keys) {
-        const uint64_t key = morton_key(g, nx, ny, (cidx[p] & CIDX_DEAD) != 0u);
-        const uint32_t k32 = (uint32_t)(key >> key32_shift(g.J));
-        mf.keys[p] = key;
-        mf.keys32[p] = k32;
-        const uint32_t b = find_bucket(mf.spl, mf.spl_nb, ((uint64_t)k32 << 32) | (uint64_t)p,
-                                       (uint32_t)(p / SORT_B));
-        mf.bkt[p] = b;
-        mf.off[p] = bucket_offset(b, mf.counts);
-    }
-}
-
 // BHA:429-432
 __global__ __launch_bounds__(TB) void k_kick(int64_t n, const double *__restrict__ a2,
                                              double *__restrict__ vx, double *__restrict__ vy,
@@ -650,23 +614,7 @@ __global__ __launch_bounds__(TB) void k_lane_compact(int64_t n, const uint32_t *
     if (q < n && flag[q]) out[qpos[q]] = pos[lanes[q]];
 }
 
-// The deep pipeline's forces (by lane) through the same lane compaction: out[qpos[q]] = a2[q].
-__global__ __launch_bounds__(TB) void k_lane_pairs(int64_t n, const uint32_t *__restrict__ flag,
-                                                   const uint32_t *__restrict__ qpos,
-                                                   const double *__restrict__ a2,
-                                                   double *__restrict__ out) {
-    int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x;
-    if (q < n && flag[q])
-        *reinterpret_cast<double2_t *>(out + 2 * (int64_t)qpos[q]) =
-            *reinterpret_cast<const double2_t *>(a2 + 2 * q);
-}
-
 }  // namespace
-
-void compact_lane_pairs(int64_t n, const uint32_t *flag, const uint32_t *qpos, const double *a2,
-                        double *out, hipStream_t s) {
-    if (n > 0) k_lane_pairs<<<grid_for(n), TB, 0, s>>>(n, flag, qpos, a2, out);
-}
 
 hipError_t compact_lanes(int64_t n, const uint32_t *lanes, const uint32_t *keep,
                          const uint32_t *pos, uint32_t *flag, uint32_t *qpos, uint32_t *out,
@@ -685,14 +633,6 @@ void kick_drift(int64_t n, const double *a2, double *x, double *y, double *vx, d
                 unsigned long long *vmax) {
     if (n > 0)
         k_kick_drift<<<grid_for(n), TB, 0, s>>>(n, a2, x, y, vx, vy, dtHalf, dt, lanes, gl, vmax);
-}
-
-void kick_drift_keys(int64_t n, const double *a2, double *x, double *y, double *vx, double *vy,
-                     const uint32_t *cidx, double dtHalf, double dt, const uint32_t *lanes,
-                     const Geometry &g, const MortonFuse &mf, hipStream_t s) {
-    if (n > 0)
-        k_kick_drift_keys<<<grid_for(n), TB, 0, s>>>(n, a2, x, y, vx, vy, cidx, dtHalf, dt, lanes,
-                                                     g, mf);
 }
 
 void copy_trav_inputs(int64_t n, const double *m, double *m_t, const uint32_t *cidx,

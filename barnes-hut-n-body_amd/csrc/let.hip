@@ -811,10 +811,7 @@ double let_include_gap2(const Geometry &g, double theta2, double soft2) {
 }
 
 // The assembly's two per-cell scans (record counts -> posc, copied-cell counts -> cpos) as one
-// scan of pairs (BH_LET_PAIR_SCAN): one lookback launch pair instead of two.
-#ifndef BH_LET_PAIR_SCAN
-#define BH_LET_PAIR_SCAN 1
-#endif
+// scan of pairs: one lookback launch pair instead of two.
 using U32Pair = rocprim::tuple<uint32_t, uint32_t>;
 struct PairPlus {
     __host__ __device__ U32Pair operator()(const U32Pair &a, const U32Pair &b) const {
@@ -909,9 +906,6 @@ hipError_t let_table(int64_t n_sub, const Geometry &g, const LetBufs &L, const T
     return hipGetLastError();
 }
 
-#ifndef BH_LET_CLEAR_AHEAD
-#define BH_LET_CLEAR_AHEAD 1
-#endif
 hipError_t let_assemble(int64_t n_sub, const Geometry &g, const LetPieces &pc, const LetBufs &L,
                         const TreeBuffers &tb, uint32_t *scal, hipStream_t s, bool *cleaned) {
     if (cleaned) *cleaned = false;
@@ -919,19 +913,9 @@ hipError_t let_assemble(int64_t n_sub, const Geometry &g, const LetPieces &pc, c
     k_let_top_lo<<<1, 256, 0, s>>>(g, L.levels);
     k_let_w<<<grid_for(LET_CELLS + 1), TB, 0, s>>>(L, tb, scal);
     size_t bytes = L.scratch_bytes;
-    hipError_t e;
-    if (BH_LET_PAIR_SCAN) {
-        e = pair_scan(L.scratch, bytes, L.w, L.ccnt, L.posc, L.cpos, (size_t)(LET_CELLS + 1), s);
-        if (e != hipSuccess) return e;
-    } else {
-        e = rocprim::exclusive_scan(L.scratch, bytes, L.w, L.posc, 0u, (size_t)(LET_CELLS + 1),
-                                    rocprim::plus<uint32_t>(), s);
-        if (e != hipSuccess) return e;
-        bytes = L.scratch_bytes;
-        e = rocprim::exclusive_scan(L.scratch, bytes, L.ccnt, L.cpos, 0u, (size_t)(LET_CELLS + 1),
-                                    rocprim::plus<uint32_t>(), s);
-        if (e != hipSuccess) return e;
-    }
+    const hipError_t e =
+        pair_scan(L.scratch, bytes, L.w, L.ccnt, L.posc, L.cpos, (size_t)(LET_CELLS + 1), s);
+    if (e != hipSuccess) return e;
     k_let_write_top_cells<<<grid_for(level_off(LET_P) + LET_CELLS), TB, 0, s>>>(L);
     k_let_copy_blocks<<<BH_LET_COPY_GRID, TB, 0, s>>>(L, tb.nodes);
     if (n_sub > 0)
@@ -940,7 +924,7 @@ hipError_t let_assemble(int64_t n_sub, const Geometry &g, const LetPieces &pc, c
         k_let_guard<<<1, 1, 0, s>>>(L, scal);
     const int64_t own_lanes = (int64_t)pc.rounds * pc.sub;
     if (own_lanes > 0 && pc.n > 0) {
-        const bool clear = BH_LET_CLEAR_AHEAD && cleaned;
+        const bool clear = cleaned != nullptr;
         k_let_lanes<<<grid_for(own_lanes), TB, 0, s>>>(pc, (uint32_t)n_sub, L.subpos, scal,
                                                         L.lanes, L,
                                                         clear ? let_sel_blocks(pc.n) : -1);

@@ -17,8 +17,6 @@
 // scalar cache / L2.  See DESIGN.md for the roofline accounting.
 // Small lists (bfs_walk below): the first walk of a step over <= 4 096 bodies serves one body
 // per wave and examines the tree level by level, the terms added in pre-order -- the same sum.
-#include <cstdlib>
-
 #include "bh_device.hpp"
 #include "fastmath.hpp"
 
@@ -70,27 +68,15 @@ __device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
     return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
 }
 
-// Which lanes are active at a stop (cur >= the lane's resume point).  BH_TRAV_STACK 0: a per-lane
-// compare at every stop and a per-lane `resume = next` in every point-force block.  1 (round 6):
-// the active set is a wave-uniform mask that changes only at "mixed" internal nodes -- some
-// active lanes accept the node, others open it: the accepting lanes park until the cursor reaches
-// the node's `next`.  Parked subtrees nest (a node pushed later lies inside the earlier ones), so
-// their `next` values form a stack: its top in an SGPR, the entries below in one VGPR, entry i in
-// lane i (v_writelane / v_readlane), the parked lanes' `next` in a per-lane VGPR written only at
-// mixed nodes.  When the cursor reaches the top, every lane whose `next` equals it is active
-// again (one compare per pop).  The mask is the per-lane compare's at every stop, exactly: a lane
-// active again keeps a stale `next` below every entry pushed after it.  At C3: ~645 stops and
-// ~548 blocks per wave against ~106 mixed nodes.  Measured (profiles/r06p_*):
-// bit-exact, VALU per wave 21572 -> 20758 (-3.8 %), but SALU 10416 -> 15537 (the pop test at
-// every stop, the park test at every internal node) and k_traverse 0.768 -> 0.797 ms (+3.7 %):
-// the wave is issue-bound over both units, so the trade loses.  Off by default.
-#ifndef BH_TRAV_STACK
-#define BH_TRAV_STACK 0
-#endif
-// (the stack holds one entry per tree level above the cursor: depth < MAX_DEPTH_TAB <= 64 lanes)
-static_assert(MAX_DEPTH_TAB <= 64, "the parked-subtree stack holds one level per lane");
-// v_writelane_b32 (the lane select goes through M0; no clang builtin on this toolchain)
-extern "C" __device__ int bh_writelane(int value, int lane, int old) __asm("llvm.amdgcn.writelane.i32");
+// Which lanes are active at a stop (cur >= the lane's resume point): a per-lane compare at every
+// stop and a per-lane `resume = next` in every point-force block.  The alternative (round 6) kept
+// the active set as a wave-uniform mask that changes only at "mixed" internal nodes -- some
+// active lanes accept the node, others open it -- with the parked subtrees' `next` values on a
+// lane-held stack.  At C3: ~645 stops and ~548 blocks per wave against ~106 mixed nodes
+// (DESIGN.md §2).  Measured (profiles/r06p_*): bit-exact, VALU per wave 21572 -> 20758 (-3.8 %),
+// but SALU 10416 -> 15537 (the pop test at every stop, the park test at every internal node) and
+// k_traverse 0.768 -> 0.797 ms (+3.7 %): the wave is issue-bound over both units, so the trade
+// loses.  That walk is in the history at 3db5b68.
 template <bool FAST, bool COUNT, bool OFF32>
 __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T, double bx,
                                      double by, double Gm, double soft2, double theta2,
@@ -98,11 +84,6 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
                                      double &fy, uint32_t &nvis, uint32_t &niters,
                                      uint32_t &ncontrib, uint32_t &nblocks) {
     uint32_t cur = 0;
-#if BH_TRAV_STACK
-    uint64_t active = __builtin_amdgcn_ballot_w64(resume == 0u);  // (idle lanes never are)
-    uint32_t top = 0xFFFFFFFFu, sp = 0u;  // the stack's top and its entries below, wave-uniform
-    uint32_t below = 0u;                  // entry i of those in lane i
-#endif
     // one iteration on record `rec`; the next record is requested into `nrec`.  The loop body
     // is unrolled twice with the two records swapping roles (no SGPR copies per iteration).
     // Loading node T (past the last one) is harmless: the node array has slack beyond T.
@@ -124,20 +105,7 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
             return;
         }
         // lane masks in SGPRs straight from the compares; per-lane booleans via inverse ballot
-#if BH_TRAV_STACK
-        while (cur >= top) {  // the cursor left a parked subtree: its lanes walk again
-            active |= __builtin_amdgcn_ballot_w64(resume == top);
-            if (sp == 0u) {
-                top = 0xFFFFFFFFu;
-            } else {
-                --sp;
-                top = (uint32_t)__builtin_amdgcn_readlane((int)below, (int)sp);
-            }
-        }
-        const uint64_t act_m = active;
-#else
         const uint64_t act_m = __builtin_amdgcn_ballot_w64(cur >= resume);
-#endif
         if (COUNT) {
             nvis += __builtin_amdgcn_inverse_ballot_w64(act_m) ? 1u : 0u;
             niters += 1;
@@ -171,17 +139,6 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
             }
             contrib_m = act_m & acc_m;
             open_m = act_m & ~acc_m;
-#if BH_TRAV_STACK
-            if (open_m != 0ull && contrib_m != 0ull) {  // mixed: the accepting lanes park
-                if (top != 0xFFFFFFFFu) {
-                    below = (uint32_t)bh_writelane((int)top, (int)sp, (int)below);
-                    ++sp;
-                }
-                top = next;  // (<= the entry below: this node lies inside that subtree)
-                active &= ~contrib_m;
-                if (__builtin_amdgcn_inverse_ballot_w64(contrib_m)) resume = next;
-            }
-#endif
         }
         const uint32_t ncur = open_m != 0ull ? cur + 1 : next;  // descend iff some lane opened
         nrec = OFF32 ? nload_off(nodes, ncur) : nload(nodes + ncur);
@@ -204,9 +161,7 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
             const double f = Gm * mass * invR2;
             fx += f * dx * invR;
             fy += f * dy * invR;
-#if !BH_TRAV_STACK
             resume = next;
-#endif
         }
         nwait(nrec);
         cur = ncur;
@@ -771,16 +726,10 @@ hipError_t selftest_fast_math(int64_t n, uint64_t seed, unsigned long long *d_ba
 #define BH_TRAV_MIN_BPW 1
 #endif
 uint32_t bodies_per_wave(int64_t lanes) {
-    // (environment overrides for A/B sweeps; BH_TRAV_MIN_WAVES=0: always 64)
-    static const int64_t min_waves = [] {
-        const char *v = std::getenv("BH_TRAV_MIN_WAVES");
-        return v ? (int64_t)std::atoll(v) : (int64_t)BH_TRAV_MIN_WAVES;
-    }();
-    static const uint32_t min_bpw = [] {
-        const char *v = std::getenv("BH_TRAV_MIN_BPW");
-        const long b = v ? std::atol(v) : (long)BH_TRAV_MIN_BPW;
-        return (uint32_t)(b < 1 ? 1 : b > TB ? TB : b);
-    }();
+    // (BH_TRAV_MIN_WAVES 0: always 64)
+    constexpr int64_t min_waves = BH_TRAV_MIN_WAVES;
+    constexpr uint32_t min_bpw =
+        (uint32_t)(BH_TRAV_MIN_BPW < 1 ? 1 : BH_TRAV_MIN_BPW > TB ? TB : BH_TRAV_MIN_BPW);
     uint32_t bpw = TB;
     while (bpw > min_bpw && (lanes + bpw - 1) / bpw < min_waves) bpw >>= 1;
     return bpw;
@@ -793,22 +742,16 @@ uint32_t bodies_per_wave(int64_t lanes) {
 //   C3 (15.6 K waves)  1.770 / 1.782 / 1.757 / 1.801
 //   C4 (156 K waves)   16.45 / 16.51 / 16.38 / 16.40;  the solo C4 / 8 rank step within noise
 //   C1 (1 563 waves of 8 bodies)  +1.5 % with 2: short walks keep one wave per group.
-// BH_TRAV_WPB (1, 2, 4, 8) overrides.
 #ifndef BH_TRAV_WPB_FULL_WAVES
 #define BH_TRAV_WPB_FULL_WAVES 8192
 #endif
 static uint32_t waves_per_group(uint32_t waves, uint32_t bpw) {
-    static const long over = [] {
-        const char *v = std::getenv("BH_TRAV_WPB");
-        return v ? std::atol(v) : 0L;
-    }();
-    if (over == 1 || over == 2 || over == 4 || over == 8) return (uint32_t)over;
     if (bpw < TB) return 1u;  // (short walks of a few bodies: C1 +1.5 % with 2)
     return waves >= BH_TRAV_WPB_FULL_WAVES ? 4u : waves >= 1024 ? 8u : 1u;
 }
 
 // Breadth-first walks (bfs_walk, one body per wave) for launches of up to BH_TRAV_BFS_MAX bodies
-// (environment override; 0: never).  Measured (profiles/r06z2_*): C1 'R' (2 000 bodies) traversal
+// (0: never).  Measured (profiles/r06z2_*): C1 'R' (2 000 bodies) traversal
 // 67.5 -> 39.8 us; C1 code default (12 500) 102 -> 135 us -- 12 500 one-body waves are ~3
 // generations of ~40 us walks, against 1 563 eight-body union walks of ~100 us.  The bitmap covers min(node capacity, 2.25 x bodies + 256, 64 K)
 // node indices -- a tree beyond it is walked by walk() body by body.
@@ -824,14 +767,8 @@ static uint32_t waves_per_group(uint32_t waves, uint32_t bpw) {
 #define BH_TRAV_BFS_MAX_KICK 0
 #endif
 constexpr uint32_t BFS_MAX_BM_WORDS = 2048;
-static int64_t env_or(const char *name, int64_t dflt) {
-    const char *e = std::getenv(name);
-    return e ? (int64_t)std::atoll(e) : dflt;
-}
 static int64_t bfs_max_bodies(int kick_mode) {
-    static const int64_t v = env_or("BH_TRAV_BFS_MAX", BH_TRAV_BFS_MAX);
-    static const int64_t vk = env_or("BH_TRAV_BFS_MAX_KICK", BH_TRAV_BFS_MAX_KICK);
-    return kick_mode == KICK_ONLY ? vk : v;
+    return kick_mode == KICK_ONLY ? BH_TRAV_BFS_MAX_KICK : BH_TRAV_BFS_MAX;
 }
 
 // (one-GPU evaluations of the whole list only: a rank's lane range walks a tree of every rank's

@@ -17,13 +17,12 @@
 //   k_prep       state permuted into the new Morton order; c(a) = common digit count of
 //                neighbours; node slot counts
 //   exclusive scan                            -> base (pre-order slot of each body's nodes)
-//   k_cells      first sorted body of every depth-D0 cell
+//   k_fixup_cells  the full keys' order inside runs of one 32-bit prefix; first sorted body
+//                of every depth-D0 cell
 //   k_emit_com   per 1024-body chunk, in LDS: internal node skeletons (depth, next) + leaf
 //                records, replay of BHA:125-156 inside each jitter cell, centre of mass
 //                bottom-up (children 0..3 in order, BHA:184-200) of the chunk-local nodes
 //   k_span_*     the chunk-spanning nodes, levels J..0
-#include <cstdlib>
-
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/block/block_radix_sort.hpp>
@@ -85,8 +84,9 @@ __global__ __launch_bounds__(TB) void k_morton(int64_t n, const double *__restri
 //                     bucket), wave-aggregated atomic count -> offset inside the bucket
 //   exclusive scan    bucket starts
 //   k_bucket_scatter  composites to their bucket's range (any order inside it)
-//   k_bucket_sort     one workgroup per bucket: bitonic sort in LDS (global memory for a
-//                     bucket above SORT_CAP -- correct, slow, never seen in smooth evolution),
+//   k_bucket_sort     one workgroup per bucket: sorted in LDS (a bitonic network on global
+//                     memory for a bucket above SORT_CAP -- correct, slow, never seen in smooth
+//                     evolution),
 //                     then keys32_s, perm and the full keys keys_s = keys[perm]
 // Splitters are (re)written by k_prep of every build; the first build after a reset uses
 // rocprim (the splitters would describe other bodies).
@@ -148,10 +148,10 @@ __global__ __launch_bounds__(SORT_TB) void k_bucket_scatter(int64_t n,
 
 // Bitonic network in its all-ascending form (the first step of every merge compares mirrored
 // pairs): a comparator never moves the larger value down, so the elements past `s` can stay
-// virtual +infinity -- sizes need no padding.  `A` is LDS or global memory of this workgroup.
+// virtual +infinity -- sizes need no padding.  `A` is global memory of this workgroup (buckets
+// that fit the LDS take one of k_bucket_sort's other paths).
 // (Measured at C4: batching a stage's loads, and skipping the barrier between stages whose
 // pairs stay inside one wave's 128-element block, were both slower than this plain form.)
-template <bool LDS>
 __device__ __forceinline__ void bitonic_sort(uint64_t *A, uint32_t s) {
     int lP = 0;
     while ((1u << lP) < s) ++lP;
@@ -171,7 +171,7 @@ __device__ __forceinline__ void bitonic_sort(uint64_t *A, uint32_t s) {
                     }
                 }
             }
-            if (!LDS) __threadfence_block();
+            __threadfence_block();
             __syncthreads();
         }
     }
@@ -181,29 +181,19 @@ __device__ __forceinline__ void bitonic_sort(uint64_t *A, uint32_t s) {
 // prefix's span inside the bucket (bins are key ranges, so bins in order are sorted relative
 // to each other), then every element's rank inside its bin -- bins hold a few elements, ties
 // of equal prefixes included, ordered by the whole composite.  A bin above RADIX_MAXBIN
-// (clustered keys) sends the bucket to the bitonic network instead.
+// (clustered keys) sends the bucket to the rank or block radix sort below instead.
 constexpr int RADIX_CAP = SORT_CAP / 2;  // the bin-grouped copy lives in the upper half of L
 constexpr int RADIX_BINS = 256;
 constexpr uint32_t RADIX_MAXBIN = 48;
 // A bucket whose key prefixes are all equal (the dead bodies' sentinel run -- the LET subset's
 // padding --, or a dense depth-16 cell) is binned by its slots instead: the composites' order is
 // then the slot order, and the bins are slot ranges.
-#ifndef BH_SORT_SLOT_RADIX
-#define BH_SORT_SLOT_RADIX 1
-#endif
 // Any other bucket of up to SORT_CAP elements (keys clustered in a few bins -- a bucket that
 // spans a gap of the subset's key ranges --, or above RADIX_CAP -- the bucket that new halo
 // cells fall into after a drift): an LDS radix sort of its composites compressed to the bits
-// they span, (key32 - min) : (slot - min); else the bitonic network.
-#ifndef BH_SORT_BLOCK_RADIX
-#define BH_SORT_BLOCK_RADIX 1
-#endif
+// they span, (key32 - min) : (slot - min).  (The bitonic network in LDS for the smallest of
+// them measured within 0.5 %; it is in the history at 3db5b68.)
 using BucketRadix = rocprim::block_radix_sort<unsigned long long, SORT_TB, SORT_CAP / SORT_TB>;
-// Buckets of up to BH_SORT_BITONIC_MAX elements that the bin radix cannot take go to the bitonic
-// network instead of the block radix sort.
-#ifndef BH_SORT_BITONIC_MAX
-#define BH_SORT_BITONIC_MAX 0
-#endif
 // Buckets of up to BH_SORT_RANK_MAX elements (a multiple of SORT_TB) that the bin radix cannot
 // take -- a few per build, whose key span holds an outlier: all but one element in one bin -- are
 // sorted by counting each element's rank in LDS instead of the block radix sort (0: off).
@@ -270,31 +260,24 @@ __global__ __launch_bounds__(SORT_TB) void k_bucket_sort(const uint32_t *__restr
             smax = max(smax, (uint32_t)v);
         }
         bool radix = s <= (uint32_t)RADIX_CAP;
-        const bool need_minmax = radix || BH_SORT_BLOCK_RADIX;
-        const bool need_slots = BH_SORT_SLOT_RADIX || BH_SORT_BLOCK_RADIX;
-        if (need_minmax) {  // wave minima / maxima first: one LDS atomic per wave
+        // wave minima / maxima first: one LDS atomic per wave
 #pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, o, 64));
-                kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
-                if (need_slots) {
-                    smin = min(smin, (uint32_t)__shfl_xor((int)smin, o, 64));
-                    smax = max(smax, (uint32_t)__shfl_xor((int)smax, o, 64));
-                }
-            }
-            if ((threadIdx.x & 63) == 0) {
-                atomicMin(&s_min, kmin);
-                atomicMax(&s_max, kmax);
-                if (need_slots) {
-                    atomicMin(&s_smin, smin);
-                    atomicMax(&s_smax, smax);
-                }
-            }
+        for (int o = 32; o > 0; o >>= 1) {
+            kmin = min(kmin, (uint32_t)__shfl_xor((int)kmin, o, 64));
+            kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, o, 64));
+            smin = min(smin, (uint32_t)__shfl_xor((int)smin, o, 64));
+            smax = max(smax, (uint32_t)__shfl_xor((int)smax, o, 64));
+        }
+        if ((threadIdx.x & 63) == 0) {
+            atomicMin(&s_min, kmin);
+            atomicMax(&s_max, kmax);
+            atomicMin(&s_smin, smin);
+            atomicMax(&s_smax, smax);
         }
         __syncthreads();
         if (radix) {
             // (uniform) equal prefixes: bin by slot (the low half of the composite)
-            const bool by_slot = BH_SORT_SLOT_RADIX && s_min == s_max;
+            const bool by_slot = s_min == s_max;
             const int hs = by_slot ? 0 : 32;
             const uint32_t lo = by_slot ? s_smin : s_min;
             const uint32_t span = by_slot ? s_smax - s_smin : s_max - s_min;
@@ -379,51 +362,45 @@ __global__ __launch_bounds__(SORT_TB) void k_bucket_sort(const uint32_t *__restr
                 if (threadIdx.x + q * SORT_TB < s) emit(r[q], v[q]);
             return;
         }
-        if (BH_SORT_BLOCK_RADIX && s > (uint32_t)BH_SORT_BITONIC_MAX) {
-            constexpr int IPT = SORT_CAP / SORT_TB;
-            const uint32_t kmn = s_min, smn = s_smin;
-            const uint32_t kspan = s_max - kmn, sspan = s_smax - smn;
-            const int sb = sspan ? 32 - __clz(sspan) : 0;  // bits of the slot offset
-            const int kb = kspan ? 32 - __clz(kspan) : 0;
-            uint64_t v[IPT];  // blocked: thread t holds elements t * IPT + q
+        constexpr int IPT = SORT_CAP / SORT_TB;
+        const uint32_t kmn = s_min, smn = s_smin;
+        const uint32_t kspan = s_max - kmn, sspan = s_smax - smn;
+        const int sb = sspan ? 32 - __clz(sspan) : 0;  // bits of the slot offset
+        const int kb = kspan ? 32 - __clz(kspan) : 0;
+        uint64_t v[IPT];  // blocked: thread t holds elements t * IPT + q
 #pragma unroll
-            for (int q = 0; q < IPT; ++q) {
-                const uint32_t j = threadIdx.x * IPT + q;
-                const uint64_t c = L[min(j, s - 1)];
-                v[q] = j < s ? ((uint64_t)((uint32_t)(c >> 32) - kmn) << sb) |
-                                   (uint64_t)((uint32_t)c - smn)
-                             : ~0ull;  // past the bucket: last (stable: after every element)
-            }
-            __syncthreads();  // L is read: its storage becomes the sort's
-            BucketRadix().sort(reinterpret_cast<unsigned long long(&)[IPT]>(v), shm.brs, 0u,
-                               (unsigned)max(kb + sb, 1));
-            const uint64_t smask = sb ? (~0ull >> (64 - sb)) : 0ull;
-#pragma unroll
-            for (int q = 0; q < IPT; ++q) {
-                const uint32_t j = threadIdx.x * IPT + q;
-                if (j < s)
-                    emit(j, ((uint64_t)((uint32_t)(v[q] >> sb) + kmn) << 32) |
-                                (uint64_t)((uint32_t)(v[q] & smask) + smn));
-            }
-            return;
+        for (int q = 0; q < IPT; ++q) {
+            const uint32_t j = threadIdx.x * IPT + q;
+            const uint64_t c = L[min(j, s - 1)];
+            v[q] = j < s ? ((uint64_t)((uint32_t)(c >> 32) - kmn) << sb) |
+                               (uint64_t)((uint32_t)c - smn)
+                         : ~0ull;  // past the bucket: last (stable: after every element)
         }
-        bitonic_sort<true>(L, s);
-        __syncthreads();
-        for (uint32_t j = threadIdx.x; j < s; j += SORT_TB) emit(j, L[j]);
-    } else {  // oversized bucket: the same network on global memory, in place
+        __syncthreads();  // L is read: its storage becomes the sort's
+        BucketRadix().sort(reinterpret_cast<unsigned long long(&)[IPT]>(v), shm.brs, 0u,
+                           (unsigned)max(kb + sb, 1));
+        const uint64_t smask = sb ? (~0ull >> (64 - sb)) : 0ull;
+#pragma unroll
+        for (int q = 0; q < IPT; ++q) {
+            const uint32_t j = threadIdx.x * IPT + q;
+            if (j < s)
+                emit(j, ((uint64_t)((uint32_t)(v[q] >> sb) + kmn) << 32) |
+                            (uint64_t)((uint32_t)(v[q] & smask) + smn));
+        }
+    } else {  // oversized bucket: the bitonic network on global memory, in place
         SORT_STAT(4, 1);
         SORT_STAT(5, s);
         SORT_LOGV(2, 1);
         SORT_LOGV(3, s);
         uint64_t *A = comp + b0;
-        bitonic_sort<false>(A, s);
+        bitonic_sort(A, s);
         for (uint32_t j = threadIdx.x; j < s; j += SORT_TB) emit(j, A[j]);  // own j: in place
     }
 }
 
 // After the 32-bit-prefix sort: keys_s = keys[perm] (k_key_gather), then every run of equal
 // prefixes (bodies sharing a depth-16 cell — short: at most 5 in C3) re-sorted by (full key,
-// original index) by the thread of its first element (k_key_fixup), so the result equals a
+// original index) by the thread of its first element (key_fixup), so the result equals a
 // stable sort of the full keys.  The run of out-of-root / merged-away bodies (one shared
 // sentinel key) is already in index order and is left alone.
 __global__ __launch_bounds__(TB) void k_key_gather(int64_t n, const uint64_t *__restrict__ keys,
@@ -456,14 +433,6 @@ __device__ __forceinline__ void key_fixup(int64_t a, int64_t n, int J,
         keys_s[j] = ki;
         perm[j] = pi;
     }
-}
-
-__global__ __launch_bounds__(TB) void k_key_fixup(int64_t n, int J,
-                                                  const uint32_t *__restrict__ keys32_s,
-                                                  uint64_t *__restrict__ keys_s,
-                                                  uint32_t *__restrict__ perm) {
-    chain_prio();
-    key_fixup((int64_t)blockIdx.x * TB + threadIdx.x, n, J, keys32_s, keys_s, perm);
 }
 
 struct HeavyList {  // TreeBuffers::heavy (null list: not wanted)
@@ -514,12 +483,9 @@ __device__ __forceinline__ uint32_t prep_one(int64_t a, int64_t n, int J,
     return c;
 }
 
-// The base scan (BH_BASE_SCAN): k_prep also sums its tile's counts into tsum[tile], and
+// The base scan: k_prep also sums its tile's counts into tsum[tile], and
 // k_base_scan turns counts and tile sums into base -- two launches without inter-block waits in
 // place of rocprim's lookback state initialisation and scan.
-#ifndef BH_BASE_SCAN
-#define BH_BASE_SCAN 1
-#endif
 constexpr int BS_TB = 1024;  // k_base_scan: BS_TB * PER counts per block
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
@@ -606,8 +572,9 @@ __global__ __launch_bounds__(BS_TB) void k_base_scan(int64_t n1, const uint32_t 
 
 // First sorted body of every depth-D0 cell (bins 0 .. 4^D0; the sentinel's prefix is 4^D0,
 // so bin 4^D0 starts at the first out-of-root body, i.e. at the in-root count).
-// Also fills the span super list [0, n_super) with 0xFF bytes for k_span_find (in place of a
-// memset launch; nothing reads it before k_span_find).
+// Also fills the span super list [0, n_super) with 0xFF bytes (in place of a memset launch):
+// k_emit_com sets only the entries of the groups that a spanning node leaves, and
+// k_com_span_top reads every entry.
 __device__ __forceinline__ void cells(int64_t bin, int64_t stride, int64_t n, int J, int D0,
                                       const uint64_t *__restrict__ keys_s,
                                       uint32_t *__restrict__ cell_start,
@@ -624,21 +591,9 @@ __device__ __forceinline__ void cells(int64_t bin, int64_t stride, int64_t n, in
     cell_start[bin] = (uint32_t)lo;
 }
 
-__global__ __launch_bounds__(TB) void k_cells(int64_t n, int J, int D0,
-                                              const uint64_t *__restrict__ keys_s,
-                                              uint32_t *__restrict__ cell_start,
-                                              uint32_t *__restrict__ super_list, int64_t n_super) {
-    chain_prio();
-    cells((int64_t)blockIdx.x * TB + threadIdx.x, (int64_t)gridDim.x * TB, n, J, D0, keys_s,
-          cell_start, super_list, n_super);
-}
-
-// k_key_fixup and k_cells in one launch (BH_FIXUP_CELLS): the depth-D0 cell starts depend on the
-// 32-bit prefixes only, final before the fixup -- which reorders bodies inside runs of one
-// prefix, so a search probing a run mid-reorder compares the same prefix whichever it reads
-#ifndef BH_FIXUP_CELLS
-#define BH_FIXUP_CELLS 1
-#endif
+// key_fixup and cells in one launch: the depth-D0 cell starts depend on the 32-bit prefixes
+// only, final before the fixup -- which reorders bodies inside runs of one prefix, so a search
+// probing a run mid-reorder compares the same prefix whichever it reads
 __global__ __launch_bounds__(TB) void k_fixup_cells(int64_t n, int J, int D0,
                                                     const uint32_t *__restrict__ keys32_s,
                                                     uint64_t *__restrict__ keys_s,
@@ -824,11 +779,8 @@ extern "C" int bh_debug_sf_times(uint64_t *out) {
 #endif
 
 static bool small_front(int64_t n, uint32_t &P) {
-    static const int64_t lim = [] {
-        const char *v = std::getenv("BH_SMALL_FRONT_MAX");
-        const int64_t x = v ? (int64_t)std::atoll(v) : (int64_t)BH_SMALL_FRONT_MAX;
-        return x < SMALL_FRONT_CAP ? x : SMALL_FRONT_CAP;
-    }();
+    constexpr int64_t lim =
+        (int64_t)BH_SMALL_FRONT_MAX < SMALL_FRONT_CAP ? (int64_t)BH_SMALL_FRONT_MAX : SMALL_FRONT_CAP;
     if (n <= 0 || n > lim) return false;
     P = 1;
     while ((int64_t)P < n) P <<= 1;
@@ -1081,10 +1033,7 @@ constexpr uint32_t SPAN_REF = 1u << 31;  // child list entry: owner slot of a sp
 // boundaries, finished by one workgroup each); such nodes are finished by k_com_span_top
 constexpr uint32_t SPAN_SUPER = 1u << 31;
 constexpr int SPAN_GROUP = 1024;
-#ifndef BH_EMIT_SPANS
-#define BH_EMIT_SPANS 1
-#endif
-struct SpanOut {  // k_emit_com's span-list outputs (BH_EMIT_SPANS)
+struct SpanOut {  // k_emit_com's span-list outputs
     uint32_t *list;
     uint32_t stride;
     uint32_t *super_list;
@@ -1239,30 +1188,27 @@ __global__ __launch_bounds__(EC_TB) void k_emit_com(int64_t n, Geometry g, int D
     }
     if (threadIdx.x == 0) s_lmax = -1;
     const uint32_t chunk = blockIdx.x;
-    if (BH_EMIT_SPANS) {  // this boundary's span list column: none until a skeleton says so
-        if ((int)threadIdx.x <= J) so.list[(size_t)threadIdx.x * so.stride + chunk] = NO_SPAN;
-        if (chunk + 1 == gridDim.x)  // (and every column past the last chunk)
-            for (uint32_t q = threadIdx.x; q < (uint32_t)(J + 1) * so.stride; q += EC_TB)
-                if (q % so.stride > chunk) so.list[q] = NO_SPAN;
-    }
+    // this boundary's span list column: none until a skeleton says so
+    if ((int)threadIdx.x <= J) so.list[(size_t)threadIdx.x * so.stride + chunk] = NO_SPAN;
+    if (chunk + 1 == gridDim.x)  // (and every column past the last chunk)
+        for (uint32_t q = threadIdx.x; q < (uint32_t)(J + 1) * so.stride; q += EC_TB)
+            if (q % so.stride > chunk) so.list[q] = NO_SPAN;
     // a chunk-spanning node at depth L, slot ni, ending at body e: listed by this boundary; the
     // owner (this chunk) rides in its comX for k_span_children; SUPER when it also contains the
     // first body past this chunk's group (k_com_span_top finishes it)
     auto span_node = [&](uint32_t ni, int L, int64_t e, uint32_t nx) __attribute__((always_inline)) {
         Node nd;
-        nd.comX = BH_EMIT_SPANS ? __longlong_as_double((long long)chunk) : 0.0;
+        nd.comX = __longlong_as_double((long long)chunk);
         nd.comY = 0.0;
         nd.mass = 0.0;
         nd.next = nx;
         nd.meta = (uint32_t)(2 * L) | NODE_SPAN;  // 2 x depth
         nodes[ni] = nd;
-        if (BH_EMIT_SPANS) {
-            const int64_t kG = (int64_t)(chunk / SPAN_GROUP) * SPAN_GROUP + SPAN_GROUP - 1;
-            const int64_t bG = (kG << COM_CHUNK_SHIFT) + (1 << COM_CHUNK_SHIFT) - 1;
-            const bool super = e > bG;
-            so.list[(size_t)L * so.stride + chunk] = ni | (super ? SPAN_SUPER : 0u);
-            if (super) so.super_list[(size_t)L * so.n_groups + (uint32_t)(kG / SPAN_GROUP)] = chunk;
-        }
+        const int64_t kG = (int64_t)(chunk / SPAN_GROUP) * SPAN_GROUP + SPAN_GROUP - 1;
+        const int64_t bG = (kG << COM_CHUNK_SHIFT) + (1 << COM_CHUNK_SHIFT) - 1;
+        const bool super = e > bG;
+        so.list[(size_t)L * so.stride + chunk] = ni | (super ? SPAN_SUPER : 0u);
+        if (super) so.super_list[(size_t)L * so.n_groups + (uint32_t)(kG / SPAN_GROUP)] = chunk;
     };
     if (lanes) {  // the traversal's lane map through this build's permutation (lane_order)
         uint32_t nl[EC_PER];
@@ -1595,57 +1541,7 @@ __global__ __launch_bounds__(EC_TB) void k_emit_com(int64_t n, Geometry g, int D
 // The nodes crossing the boundary between chunk k and k+1 (bodies b = end of chunk k and
 // b+1) are exactly b's ancestors at depths 0..c(b); each chunk-spanning node is listed once,
 // by the boundary of the chunk it starts in: span_list[L * stride + k] (or NO_SPAN).  k_emit_com
-// lists them as it writes their skeletons (BH_EMIT_SPANS); k_span_find is the separate pass.
-
-__global__ __launch_bounds__(TB) void k_span_find(int64_t n, int J, int D0,
-                                                  const uint64_t *__restrict__ keys_s,
-                                                  const int8_t *__restrict__ cpl,
-                                                  const uint32_t *__restrict__ base,
-                                                  const uint32_t *__restrict__ cell_start,
-                                                  uint32_t *__restrict__ span_list,
-                                                  uint32_t span_stride,
-                                                  uint32_t *__restrict__ super_list,
-                                                  uint32_t n_groups, Node *nodes) {
-    chain_prio();
-    const int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x;
-    const int L = blockIdx.y;
-    if (k >= (int64_t)span_stride) return;
-    const int64_t chunk0 = k << COM_CHUNK_SHIFT;
-    const int64_t b = chunk0 + (1 << COM_CHUNK_SHIFT) - 1;
-    const int cb = (b + 1 < n) ? (int)cpl[b] : -1;
-    uint32_t out = NO_SPAN;
-    if (L <= cb) {
-        const uint64_t key = keys_s[b];
-        int64_t aL;  // first body of b's depth-L cell
-        if (L <= D0) {
-            aL = cell_start[(key >> (2 * (J - L))) << (2 * (D0 - L))];
-        } else {
-            const int shift = 2 * (J - L);
-            const uint64_t pref = key >> shift;
-            int64_t lo = cell_start[key >> (2 * (J - D0))], hi = b;
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if ((keys_s[mid] >> shift) < pref) lo = mid + 1; else hi = mid;
-            }
-            aL = lo;
-        }
-        if (aL >= chunk0) {  // starts in chunk k: this boundary owns it
-            const int cp = aL > 0 ? (int)cpl[aL - 1] : -1;
-            const uint32_t ni = base[aL] + (uint32_t)(L - cp - 1);
-            // the owner slot rides in the (not yet computed) comX of the span node, so its
-            // parent's child list can refer to the slot (k_span_children)
-            nodes[ni].comX = __longlong_as_double((long long)k);
-            // does the node also contain the first group boundary at or after chunk k?
-            const int64_t kG = (k / SPAN_GROUP) * SPAN_GROUP + SPAN_GROUP - 1;
-            const int64_t bG = (kG << COM_CHUNK_SHIFT) + (1 << COM_CHUNK_SHIFT) - 1;
-            const int shift = 2 * (J - L);
-            const bool super = bG + 1 < n && (keys_s[bG + 1] >> shift) == (key >> shift);
-            out = ni | (super ? SPAN_SUPER : 0u);
-            if (super) super_list[(size_t)L * n_groups + (uint32_t)(kG / SPAN_GROUP)] = (uint32_t)k;
-        }
-    }
-    span_list[(size_t)L * span_stride + k] = out;
-}
+// lists them as it writes their skeletons.
 
 // Children of every chunk-spanning node with the values of the local ones (final after
 // k_emit_com), gathered in parallel so the level-by-level pass below reads one
@@ -1759,19 +1655,9 @@ __global__ __launch_bounds__(SPAN_TB) void k_com_span(int J, const uint32_t *__r
 #endif
     auto fetch = [&](SpanRegs &r, int L) __attribute__((always_inline)) {
         r.ni = NO_SPAN;
-#ifdef BH_SPAN_NOLOAD  // (timing experiment only: results wrong)
-        if (L >= 0 && ((own >> L) & 1ull)) {
-            r.ni = 0u;
-            for (int c = 0; c < 4; ++c) {
-                r.ch[c] = 0xFFFFFFFFu;
-                r.v[c][0] = r.v[c][1] = r.v[c][2] = 1.0;
-            }
-        }
-#else
         if (L >= 0 && ((own >> L) & 1ull))
             load_span(r, span_list, span_children, (size_t)(J + 1) * span_stride,
                       (size_t)L * span_stride + k);
-#endif
     };
     auto level = [&](const SpanRegs &C, int L) __attribute__((always_inline)) {
         const int cur = L & 1, prev = cur ^ 1;
@@ -1887,15 +1773,12 @@ __global__ __launch_bounds__(SPAN_TB) void k_com_span_top(int J,
     }
 }
 
-// The same pass with everything but the chain itself loaded up front (BH_SPAN_TOP_LDS, up to
+// The same pass with everything but the chain itself loaded up front (up to
 // SPAN_TOP_PAIRS (level, group boundary) pairs): every pair's record, and the values of its
 // children that are not group-crossing (local ones from the record, span ones from the node
 // array: k_com_span finished them), are staged in LDS by all threads at once; the levels then
 // run on LDS only -- a group-crossing child of (L, g) is the pair (L + 1, its owner's group).
 // The old pass made ~5 dependent global loads per level, a 22-level chain of ~1 us steps.
-#ifndef BH_SPAN_TOP_LDS
-#define BH_SPAN_TOP_LDS 1
-#endif
 constexpr int SPAN_TOP_PAIRS = 256;
 constexpr uint32_t TOP_CONST = 0xFFFFFFFFu;  // child value staged (no pair reference)
 __global__ __launch_bounds__(SPAN_TB) void k_com_span_top_lds(
@@ -2007,7 +1890,7 @@ size_t base_scan_sums_bytes(int64_t n) {
 // (above 4 M counts rocprim's single pass is faster: the blocks' prefix reads grow with n^2 /
 // block size -- C4 16.52-16.54 against 16.57-16.58 ms per step, profiles/r05y4_ab_c4.txt)
 bool own_base_scan(int64_t n, size_t scratch_bytes) {
-    return BH_BASE_SCAN && n + 1 <= ((int64_t)1 << 22) &&
+    return n + 1 <= ((int64_t)1 << 22) &&
            scratch_bytes >= sizeof(uint32_t) * (size_t)prep_blocks_for(n);
 }
 
@@ -2401,12 +2284,9 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
     // the sort above wrote keys, permutation and bucket tables only: what follows writes
     // super_list, then span_list and span_children
     if (!small && b.late_ev && (st = hipStreamWaitEvent(s, b.late_ev, 0)) != hipSuccess) return st;
-    if (small) {
-    } else if (BH_FIXUP_CELLS)
+    if (!small)
         k_fixup_cells<<<grid_for(std::max<int64_t>(n, nbins1)), TB, 0, s>>>(
             n, g.J, D0, b.keys32_s, b.keys_s, b.perm, b.cell_start, b.super_list, n_super);
-    else
-        k_key_fixup<<<grid_for(n), TB, 0, s>>>(n, g.J, b.keys32_s, b.keys_s, b.perm);
     const int64_t prep_blocks = prep_blocks_for(n);
     const bool own_scan = own_base_scan(n, b.scratch_bytes);
     uint32_t *tsum = own_scan ? static_cast<uint32_t *>(b.scratch) : nullptr;
@@ -2425,18 +2305,11 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
                                      rocprim::plus<uint32_t>(), s);
         if (st != hipSuccess) return st;
     }
-    if (!BH_FIXUP_CELLS && !small)
-        k_cells<<<grid_for(nbins1), TB, 0, s>>>(n, g.J, D0, b.keys_s, b.cell_start, b.super_list,
-                                                n_super);
     k_emit_com<<<(unsigned)com_chunks(n), EC_TB, 0, s>>>(
         n, g, D0, b.keys_s, b.cpl, b.base, b.cell_start, b.dst.x, b.dst.y, b.dst.m, b.dst.cidx,
         b.idx, b.nodes, b.scalars + 1, b.keys32, b.lanes_remap,
         SpanOut{b.span_list, b.span_stride, b.super_list, n_groups}, b.tc);
     const dim3 span_grid((b.span_stride + TB - 1) / TB, g.J + 1);
-    if (!BH_EMIT_SPANS)
-        k_span_find<<<span_grid, TB, 0, s>>>(n, g.J, D0, b.keys_s, b.cpl, b.base, b.cell_start,
-                                             b.span_list, b.span_stride, b.super_list, n_groups,
-                                             b.nodes);
     // from here on only nodes, span_children and the lists above are touched
     // (the event attached to k_emit_com's launch instead, hipExtLaunchKernelGGL's stop event,
     // costs the build the same ~7 us at C3: not used)
@@ -2445,7 +2318,7 @@ hipError_t tree_build(const TreeBuffers &b, int64_t n, const Geometry &g, hipStr
                                              b.span_children);
     k_com_span<<<n_groups, SPAN_TB, 0, s>>>(g.J, b.span_list, b.span_stride, b.span_children,
                                             b.nodes);
-    if (n_groups > 1 && BH_SPAN_TOP_LDS && (int64_t)(g.J + 1) * n_groups <= SPAN_TOP_PAIRS)
+    if (n_groups > 1 && (int64_t)(g.J + 1) * n_groups <= SPAN_TOP_PAIRS)
         k_com_span_top_lds<<<1, SPAN_TB, 0, s>>>(g.J, b.span_list, b.span_stride,
                                                  b.span_children, b.super_list, n_groups,
                                                  b.nodes);
