@@ -50,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "bh_progress", "bh_compute_potential", "bh_compute_diagnostics", "bh_potential_kernel_ms",
     "bh_nbody3d_center_of_mass", "bh_default_view", "bh_render_bodies", "bh_render_kernel_ms",
     "bh_launch_plan", "bh_render_quads", "bh_render_quads_kernel_ms",
+    "bh_compute_field", "bh_field_kernel_ms",
 )
 
 
@@ -192,6 +193,8 @@ def load_library(path: str | None = None):
     lib.bh_compute_potential.argtypes = [_VP, _D]
     lib.bh_compute_diagnostics.argtypes = [_VP, ctypes.c_int, ctypes.POINTER(BhDiagnostics)]
     lib.bh_potential_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_compute_field.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
+    lib.bh_field_kernel_ms.argtypes = [_VP, _D]
     lib.bh_default_view.argtypes = [ctypes.POINTER(BhView)]
     lib.bh_default_view.restype = None
     lib.bh_render_bodies.argtypes = [_VP, ctypes.POINTER(BhView), ctypes.POINTER(ctypes.c_uint8),
@@ -631,6 +634,35 @@ class Engine:
         """HIP-event time (ms) of the last potential kernel launch (bh_potential_kernel_ms)."""
         ms = ctypes.c_double(0.0)
         self._check(self._lib.bh_potential_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def compute_field(self, px, py, pm=None, want_accel=True, want_phi=True):
+        """bh_compute_field: (ax, ay, phi) at the probe points (px, py), in probe order; None
+        for what was not asked (want_accel: ax and ay, want_phi: phi).  A probe is a body of
+        mass pm (None: 1.0, the field per unit mass) that is not in the tree: it takes every
+        non-empty leaf -- a probe on a body gets that body's full term -- and the cells the
+        force walk accepts, a = F / pm, phi = -G sum m / sqrt(r2 + soft2).  A build, exactly as
+        compute_potential (the jitter may move positions); the probes never enter the state."""
+        px = np.ascontiguousarray(px, dtype=np.float64)
+        py = np.ascontiguousarray(py, dtype=np.float64)
+        n = len(px)
+        if px.ndim != 1 or py.shape != px.shape:
+            raise ValueError("px and py must be 1-d arrays of equal length")
+        if pm is not None:
+            pm = np.ascontiguousarray(pm, dtype=np.float64)
+            if pm.shape != px.shape:
+                raise ValueError("pm must have the length of px")
+        ax = np.empty(n, dtype=np.float64) if want_accel else None
+        ay = np.empty(n, dtype=np.float64) if want_accel else None
+        phi = np.empty(n, dtype=np.float64) if want_phi else None
+        self._check(self._lib.bh_compute_field(self._h, n, _dp(px), _dp(py), _dp(pm), _dp(ax),
+                                               _dp(ay), _dp(phi)))
+        return ax, ay, phi
+
+    def field_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last field kernel launch (bh_field_kernel_ms)."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.bh_field_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
     def render_bodies(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,

@@ -437,6 +437,11 @@ struct TraverseShape {
 };
 TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
                              bool ordered);
+// The cursor walk's grouping for a launch of `lanes` lanes: bodies per wave (fewer than 64 for
+// small launches) and waves per workgroup (traverse_shape's own choices; field.hip launches by
+// them too).
+uint32_t bodies_per_wave(int64_t lanes);
+uint32_t waves_per_group(uint32_t waves, uint32_t bpw);
 void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x, double *y,
               const double *m, const uint32_t *cidx, int64_t lo, int64_t hi, const Geometry &g,
               const ForceParams &fp, double *a2, const TraverseCounters *cnt,
@@ -615,6 +620,25 @@ void potential_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, con
 size_t diag_partial_doubles();
 void diag_reduce(int64_t n, const double *x, const double *y, const double *vx, const double *vy,
                  const double *m, const double *phi, double *part, double *out8, hipStream_t s);
+
+// ---- launchers (field.hip) -------------------------------------------------------
+// The field at n probe points that are not in the tree (bh_compute_field): probe j = (px[j],
+// py[j]) of mass pm[j] (pm null: 1.0) takes every non-empty leaf and every internal node with
+// s2 < theta2 * dist2, in pre-order, and gets ax[j], ay[j] = F / pm (BHA:250-259, 390-391) and
+// phi[j] = -(G * sum of mass / sqrt(dist2 + soft2)), all three written by probe index.  Lane q
+// walks probe order[q] (a permutation of 0..n-1; only the grouping into waves depends on it).
+// d_T null: no tree (nodes is not read).  The launch shape is the traversal's for n lanes.
+void field_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const double *px,
+                const double *py, const double *pm, const uint32_t *order, int64_t n,
+                const Geometry &g, const ForceParams &fp, double *ax, double *ay, double *phi,
+                hipStream_t s);
+// order = the probe indices sorted by the 32-bit prefix of the build's own Morton key of their
+// positions (non-finite and out-of-root probes: the sentinel, last), ties in index order.
+// key, key_s, idx: n entries of scratch each; scratch: field_sort_bytes(n).
+size_t field_sort_bytes(int64_t n);
+hipError_t field_order(int64_t n, const double *px, const double *py, const Geometry &g,
+                       uint32_t *key, uint32_t *key_s, uint32_t *idx, uint32_t *order,
+                       void *scratch, size_t scratch_bytes, hipStream_t s);
 
 // ---- launchers (render.hip) ------------------------------------------------------
 // The body pass of a frame (PNL:302-307).  Working planes `packed` and `cnt` (null: no density):

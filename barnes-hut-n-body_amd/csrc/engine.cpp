@@ -224,6 +224,17 @@ struct bh_engine {
     hipEvent_t pot_ev[2] = {nullptr, nullptr};  // around the last potential kernel
     bool pot_timed = false;
 
+    // bh_compute_field (field.hip): the call's own probe buffers, allocated on first use and
+    // grown when needed; nothing of the engine's state or bookkeeping is kept here
+    double *fld_in = nullptr;    // px, py, pm planes of fld_cap probes
+    double *fld_out = nullptr;   // ax, ay, phi planes, by probe index
+    uint32_t *fld_u32 = nullptr; // key, sorted key, index, order planes
+    void *fld_scratch = nullptr;
+    size_t fld_scratch_bytes = 0;
+    int64_t fld_cap = 0;
+    hipEvent_t fld_ev[2] = {nullptr, nullptr};  // around the last field kernel
+    bool fld_timed = false;
+
     // bh_render_bodies (render.hip): buffers of its own, allocated on first use, kept while the
     // padded pixel count is unchanged.  rnd_packed / rnd_cnt are zero between calls (the resolve
     // kernel re-zeroes what the rasteriser touched); rnd_clean = false: a call failed in between
@@ -1537,9 +1548,59 @@ int potential_bufs(bh_engine *e) {
     return BH_OK;
 }
 
+// bh_compute_field's route through evaluate(): the tree exactly as for PotentialEval, then the
+// field at the caller's probes (host arrays; pm nullable) into e->fld_out by probe index.  run =
+// false or no probes: build only.  The probes live in buffers of the call's own (field_bufs).
+struct FieldEval {
+    bool run;
+    int64_t n_probe;
+    const double *px, *py, *pm;
+};
+
+int field_bufs(bh_engine *e, int64_t n_probe) {
+    if (n_probe > e->fld_cap || !e->fld_in) {
+        const size_t cap = (size_t)n_probe;
+        TRY(dev_alloc(e, e->fld_in, 3 * cap));
+        TRY(dev_alloc(e, e->fld_out, 3 * cap));
+        TRY(dev_alloc(e, e->fld_u32, 4 * cap));
+        if (e->fld_scratch) (void)hipFree(e->fld_scratch);
+        e->fld_scratch = nullptr;
+        e->fld_cap = 0;
+        e->fld_scratch_bytes = field_sort_bytes(n_probe);
+        HIPCHK(e, hipMalloc(&e->fld_scratch, e->fld_scratch_bytes ? e->fld_scratch_bytes : 1));
+        e->fld_cap = n_probe;
+    }
+    for (hipEvent_t &ev : e->fld_ev)
+        if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return BH_OK;
+}
+
+// Upload, key and sort the probes, then the field kernel between its two events (d_T null: no
+// tree -- no bodies).
+int field_launch(bh_engine *e, const FieldEval &f, const Node *nodes, size_t node_cap,
+                 const uint32_t *d_T, const ForceParams &fp) {
+    const int64_t P = f.n_probe;
+    TRY(field_bufs(e, P));
+    const size_t cap = (size_t)e->fld_cap, bytes = sizeof(double) * (size_t)P;
+    double *px = e->fld_in, *py = px + cap, *pm = f.pm ? py + cap : nullptr;
+    HIPCHK(e, hipMemcpyAsync(px, f.px, bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(py, f.py, bytes, hipMemcpyHostToDevice, e->stream));
+    if (pm) HIPCHK(e, hipMemcpyAsync(pm, f.pm, bytes, hipMemcpyHostToDevice, e->stream));
+    uint32_t *key = e->fld_u32, *key_s = key + cap, *idx = key_s + cap, *order = idx + cap;
+    HIPCHK(e, field_order(P, px, py, e->geo, key, key_s, idx, order, e->fld_scratch,
+                          e->fld_scratch_bytes, e->stream));
+    HIPCHK(e, hipEventRecord(e->fld_ev[0], e->stream));
+    field_walk(nodes, node_cap, d_T, px, py, pm, order, P, e->geo, fp, e->fld_out,
+               e->fld_out + cap, e->fld_out + 2 * cap, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->fld_ev[1], e->stream));
+    e->fld_timed = true;
+    return BH_OK;
+}
+
 int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fused = nullptr,
              bool allow_let = false, bool *let_used = nullptr,
-             const PotentialEval *pot = nullptr) {
+             const PotentialEval *pot = nullptr, const FieldEval *fld = nullptr) {
     if (fused) *fused = false;
     if (let_used) *let_used = false;
     // (the pieces are ranges of the slot order: spatially compact only once a full build has
@@ -1602,6 +1663,11 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
         HIPCHK(e, hipEventRecord(e->pot_ev[1], e->stream));
         e->pot_timed = true;
         return BH_OK;
+    }
+    if (fld) {  // the field at the probes on this tree, by this engine alone (theta = 0: the
+                // same walk, which then opens every internal node)
+        if (!fld->run || fld->n_probe == 0) return BH_OK;
+        return field_launch(e, *fld, e->nodes, e->node_cap, d_T, fp);
     }
     const bool direct = fp.theta2 == 0.0 && !visits;
     if (direct) {
@@ -3067,10 +3133,12 @@ void bh_destroy(bh_engine *e) {
                     e->mir_keep, e->mir_pos, e->mir_tmp, e->mir_idx_stage, e->lanes_next, e->lr_hkey, e->lr_hkey_s,
                     e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
-                    e->qd_out, e->qd_count};
+                    e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (hipEvent_t ev : e->pot_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->fld_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->rnd_ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -3715,6 +3783,74 @@ int bh_potential_kernel_ms(const bh_engine *e, double *ms) {
     if (!e->pot_timed) return BH_OK;
     float f = 0.f;
     if (hipEventElapsedTime(&f, e->pot_ev[0], e->pot_ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *ms = (double)f;
+    return BH_OK;
+}
+
+// bh_compute_field on one engine, state semantics of compute_accelerations_rank.  run: this
+// engine evaluates the probes (else it only builds); ax, ay, phi (each nullable): copy-out in the
+// caller's probe order.
+static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi) {
+    e->prog_api.store(++e->api_calls);
+    HIPCHK(e, hipSetDevice(e->device));
+    const int64_t n = e->n, P = fe.n_probe;
+    const bool run = fe.run && P > 0;
+    e->ev_used = 0;
+    e->timings_pending = false;
+    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
+    if (n > 0) {
+        TRY(evaluate(e, nullptr, KICK_NONE, nullptr, false, nullptr, nullptr, &fe));
+        e->mir_fresh = false;
+        SYNC(e, e->stream);
+        TRY(check_tree_flags(e));
+    } else if (run) {  // no bodies, no tree: every sum stays +0.0
+        const ForceParams fp{e->p.G, e->p.soft2, e->p.theta * e->p.theta};
+        TRY(field_launch(e, fe, nullptr, 0, nullptr, fp));
+        SYNC(e, e->stream);
+    }
+    if (run) {
+        const size_t cap = (size_t)e->fld_cap, bytes = sizeof(double) * (size_t)P;
+        double *out[3] = {ax, ay, phi};
+        for (int k = 0; k < 3; ++k)
+            if (out[k])
+                HIPCHK(e, hipMemcpy(out[k], e->fld_out + k * cap, bytes, hipMemcpyDeviceToHost));
+    }
+    if (e->profiling) TRY(collect_timings(e));
+    return BH_OK;
+}
+
+static int field_call(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi) {
+    ASYNC_GUARD(e);
+    COMM_GUARD(e);
+    return fail_multi_rank(e, field_rank(e, fe, ax, ay, phi));
+}
+
+int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const double *py,
+                     const double *pm, double *ax, double *ay, double *phi) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (n_probe < 0 || n_probe > ((int64_t)1 << 28)) {
+        e->err = "bh_compute_field: n_probe must be in [0, 2^28]";
+        return BH_E_INVALID;
+    }
+    if (n_probe > 0 && (!px || !py)) {
+        e->err = "bh_compute_field: px or py is NULL";
+        return BH_E_INVALID;
+    }
+    const FieldEval all{true, n_probe, px, py, pm}, none{false, 0, nullptr, nullptr, nullptr};
+    // (every member builds, member 0 evaluates and answers: as bh_compute_potential)
+    MULTI_ALL(e, r_ == 0 ? field_call(m_, all, ax, ay, phi)
+                         : field_call(m_, none, nullptr, nullptr, nullptr));
+    return field_call(e, all, ax, ay, phi);
+}
+
+int bh_field_kernel_ms(const bh_engine *e, double *ms) {
+    if (!e || !ms) return BH_E_INVALID;
+    e = MULTI_M0(e);
+    *ms = 0.0;
+    if (!e->fld_timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, e->fld_ev[0], e->fld_ev[1]) != hipSuccess) return BH_E_DEVICE;
     *ms = (double)f;
     return BH_OK;
 }

@@ -1,0 +1,238 @@
+// Field query over the flattened quadtree: acceleration and potential at probe points that are
+// not bodies of the system (bh_compute_field, include/bh_engine.h).
+//
+// Probe j is a Body(px, py, 0, 0, pm) that is NOT in the tree.  BHTree.accumulateForce for such a
+// body (BHA:215-239) skips massless nodes (BHA:216), never meets "its own leaf" -- the identity
+// test of BHA:219 cannot match -- so it takes EVERY non-empty leaf, and takes an internal node iff
+// s2 < theta2 * dist2 (BHA:226-228), else visits its children in order.  Every taken node adds,
+// in that pre-order,
+//     dx = comX - px;  dy = comY - py;  r2 = dx*dx + dy*dy + soft2
+//     invR = 1.0 / sqrt(r2);  invR2 = 1.0 / r2;  f = (G * pm) * m * invR2          (BHA:250-259)
+//     fx += f * dx * invR;  fy += f * dy * invR;  s += m * invR                     (from +0.0)
+// and a = F / pm (BHA:390-391), phi = -(G * s) (the term of bh_compute_potential).  This is what
+// the engine already computes for a body outside the root cell (BHA:126: not inserted, walked).
+//
+// The walk is traverse.hip's walk(): one lane = one probe, one wave-shared pre-order cursor, the
+// node record through a scalar load requested one stop ahead, every lane's own criterion by
+// ballot.  It is a walk of its own because a probe has no slot: walk<false> skips the leaf whose
+// body slot equals the lane's slot and k_potential compares every leaf against it, while probe i
+// must feel the body in slot i; and the fast force walk relies on the own leaf's term being +-0,
+// while a probe that sits on a body owes that body's full potential term m / sqrt(soft2).  So no
+// path here compares a leaf with anything, and no term is ever excused.
+// One point-force block serves both results: the potential's term reuses the block's invR (one
+// multiply and one add more; never fused: the build contracts nothing).
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "bh_device.hpp"
+#include "fastmath.hpp"
+
+namespace bh {
+namespace {
+
+constexpr int TB = 64;
+constexpr int MAX_WPB = 8;           // waves per workgroup (traverse.hip waves_per_group)
+constexpr uint32_t FLD_XCD_RUN = 64; // consecutive waves per XCD (traverse.hip BH_TRAV_XCD_RUN)
+static_assert(FLD_XCD_RUN % MAX_WPB == 0, "an XCD run holds whole workgroups");
+constexpr int KEY_TB = 256;
+
+typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
+
+// Node record through an explicit scalar load whose wait is placed by hand (traverse.hip nload).
+__device__ __forceinline__ u32x8 nload(const Node *p) {
+    u32x8 v;
+    asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
+    return v;
+}
+__device__ __forceinline__ u32x8 nload_off(const Node *base, uint32_t idx) {
+    u32x8 v;
+    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(base), "s"(idx << 5) : "memory");
+    return v;
+}
+__device__ __forceinline__ void nwait(u32x8 &v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v)); }
+__device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
+    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
+}
+
+// FAST: the wave's operands are inside the range guards of fastmath.hpp (fast_s2_ok,
+// lane_fast_ok) and every lane's G * pm is finite: the seeded sqrt / reciprocal sequences equal
+// the IEEE operations and the criterion's s2 is formed by an exponent subtraction.  A massless
+// node then needs no test, as in walk(): it carries the leaf flag (bh_device.hpp NODE_SKIP), so
+// the cursor moves past its subtree, and its terms -- f = (G pm) * 0 * invR2, 0 * invR, all
+// factors finite -- are exact +-0 that leave the sums (from +0.0, never -0.0) unchanged.
+// lane_self_ok has no counterpart: a coincident body's term is owed, whatever it is, and both
+// paths compute it with the same operations.
+template <bool FAST, bool OFF32>
+__device__ __forceinline__ void field_walk_wave(const Node *__restrict__ nodes, uint32_t T,
+                                                double bx, double by, double Gm, double soft2,
+                                                double theta2, double s2root, uint32_t resume,
+                                                double &fx, double &fy, double &s) {
+    uint32_t cur = 0;
+    // one iteration on record `rec`; the next record is requested into `nrec` (the node array
+    // has slack beyond T, so loading node T is harmless)
+    auto iter = [&](const u32x8 &rec, u32x8 &nrec) __attribute__((always_inline)) {
+        const double comX = as_f64(rec[0], rec[1]), comY = as_f64(rec[2], rec[3]);
+        const double mass = as_f64(rec[4], rec[5]);
+        uint32_t meta = rec[7];
+        asm volatile("" : "+s"(meta));  // keep the flag tests scalar
+        uint32_t next = rec[6];
+        next = next > cur ? next : cur + 1;  // structural guard: the cursor always advances
+        if (!FAST && (meta & NODE_SKIP)) {   // mass == 0.0 (BHA:216): not visited
+            cur = next;
+            nrec = OFF32 ? nload_off(nodes, cur) : nload(nodes + cur);
+            nwait(nrec);
+            return;
+        }
+        const uint64_t act_m = __builtin_amdgcn_ballot_w64(cur >= resume);
+        const double dx = comX - bx;  // BHA:223-225 == BHA:251-253
+        const double dy = comY - by;
+        const double d2 = dx * dx + dy * dy + soft2;
+        uint64_t contrib_m, open_m;  // lanes that take / open this node
+        if (meta & NODE_LEAF) {      // a probe is in no leaf: every non-empty leaf is taken
+            contrib_m = act_m;
+            open_m = 0;
+        } else {  // BHA:226-228, decided exactly as traverse.hip's walk decides it
+            uint64_t acc_m;
+            if (FAST) {
+                const uint64_t s2b = (uint64_t)__double_as_longlong(s2root) -
+                                     ((uint64_t)(meta & NODE_DEPTH2_MASK) << 52);
+                acc_m = __builtin_amdgcn_ballot_w64(__longlong_as_double((long long)s2b) <
+                                                    theta2 * d2);
+            } else {
+                const double t2 = __builtin_ldexp(theta2 * d2, (int)(meta & NODE_DEPTH2_MASK));
+                acc_m = __builtin_amdgcn_ballot_w64(s2root < t2);
+            }
+            contrib_m = act_m & acc_m;
+            open_m = act_m & ~acc_m;
+        }
+        const uint32_t ncur = open_m != 0ull ? cur + 1 : next;  // descend iff some lane opened
+        nrec = OFF32 ? nload_off(nodes, ncur) : nload(nodes + ncur);
+        if (__builtin_amdgcn_inverse_ballot_w64(contrib_m)) {  // BHA:250-259, order as written
+            double invR, invR2;
+            if (FAST) {
+                double h;
+                const double r = sqrt_rn_inrange_h(d2, h);
+                invR = rcp_rn_seeded(r, h + h);
+                invR2 = rcp_rn_seeded(d2, invR * invR);
+            } else {
+                invR = 1.0 / sqrt(d2);
+                invR2 = 1.0 / d2;
+            }
+            const double f = Gm * mass * invR2;
+            fx += f * dx * invR;
+            fy += f * dy * invR;
+            s += mass * invR;  // bh_compute_potential's term, from the block's own invR
+            resume = next;
+        }
+        nwait(nrec);
+        cur = ncur;
+    };
+    if (T == 0) return;  // no body inside the root cell: an empty tree
+    u32x8 r0 = nload(nodes), r1;
+    nwait(r0);
+    while (true) {
+        iter(r0, r1);
+        if (cur >= T) break;
+        iter(r1, r0);
+        if (cur >= T) break;
+    }
+}
+
+// Wave v walks the bpw lanes [bpw v, bpw v + bpw); lane q holds probe order[q] and writes its
+// results straight to that caller index.  d_T null: no tree was built (no bodies).
+template <bool OFF32>
+__global__ __launch_bounds__(TB * MAX_WPB) void k_field(const Node *__restrict__ nodes,
+                                                        const uint32_t *__restrict__ d_T,
+                                                        const double *__restrict__ px,
+                                                        const double *__restrict__ py,
+                                                        const double *__restrict__ pm,
+                                                        const uint32_t *__restrict__ order,
+                                                        int64_t n, ForceParams fp, double s2root,
+                                                        double *__restrict__ ax,
+                                                        double *__restrict__ ay,
+                                                        double *__restrict__ phi, uint32_t bpw,
+                                                        uint32_t wpb) {
+    uint32_t b = blockIdx.x;  // runs of FLD_XCD_RUN consecutive waves per XCD (bh_device.hpp)
+    {
+        const uint32_t C = FLD_XCD_RUN / wpb, G = 8 * C, full = gridDim.x / G;
+        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
+    }
+    const uint32_t v = b * wpb + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t q = (int64_t)v * bpw + lane;
+    const bool valid = lane < bpw && q < n;
+    const int64_t j = valid ? (int64_t)order[q] : 0;  // the probe's caller index
+    const double bx = valid ? px[j] : 0.0;
+    const double by = valid ? py[j] : 0.0;
+    const double bm = valid && pm ? pm[j] : 1.0;
+    const double Gm = fp.G * bm;  // (Config.G * b.m) is evaluated first (BHA:256)
+    const double soft2 = fp.soft2, theta2 = fp.theta2;
+    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
+    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
+    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
+                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
+    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
+    double fx = 0.0, fy = 0.0, s = 0.0;
+    if (fast)
+        field_walk_wave<true, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
+                                     s);
+    else
+        field_walk_wave<false, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
+                                      s);
+    if (!valid) return;
+    ax[j] = fx / bm;  // BHA:390-391
+    ay[j] = fy / bm;
+    phi[j] = -(fp.G * s);
+}
+
+// The build's own key of a probe's position (total: a NaN or out-of-root probe takes the
+// sentinel), its 32-bit prefix as the build sorts it, and the probe's index.
+__global__ __launch_bounds__(KEY_TB) void k_field_keys(int64_t n, const double *__restrict__ px,
+                                                       const double *__restrict__ py, Geometry g,
+                                                       uint32_t *__restrict__ key,
+                                                       uint32_t *__restrict__ idx) {
+    const int64_t i = (int64_t)blockIdx.x * KEY_TB + threadIdx.x;
+    if (i >= n) return;
+    key[i] = (uint32_t)(morton_key(g, px[i], py[i], false) >> key32_shift(g.J));
+    idx[i] = (uint32_t)i;
+}
+
+}  // namespace
+
+size_t field_sort_bytes(int64_t n) {
+    size_t bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, bytes, (uint32_t *)nullptr, (uint32_t *)nullptr,
+                                    (uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)n, 0u, 32u);
+    return bytes;
+}
+
+hipError_t field_order(int64_t n, const double *px, const double *py, const Geometry &g,
+                       uint32_t *key, uint32_t *key_s, uint32_t *idx, uint32_t *order,
+                       void *scratch, size_t scratch_bytes, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    k_field_keys<<<(unsigned)((n + KEY_TB - 1) / KEY_TB), KEY_TB, 0, s>>>(n, px, py, g, key, idx);
+    hipError_t st = hipGetLastError();
+    if (st != hipSuccess) return st;
+    size_t bytes = scratch_bytes;
+    return rocprim::radix_sort_pairs(scratch, bytes, key, key_s, idx, order, (size_t)n, 0u, 32u,
+                                     s);
+}
+
+void field_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const double *px,
+                const double *py, const double *pm, const uint32_t *order, int64_t n,
+                const Geometry &g, const ForceParams &fp, double *ax, double *ay, double *phi,
+                hipStream_t s) {
+    if (n <= 0) return;
+    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
+    const uint32_t bpw = bodies_per_wave(n);
+    const uint32_t waves = (uint32_t)((n + bpw - 1) / bpw);
+    const uint32_t wpb = waves_per_group(waves, bpw);
+    const unsigned grid = (waves + wpb - 1) / wpb;
+    if (off32)
+        k_field<true><<<grid, TB * wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0], ax,
+                                                ay, phi, bpw, wpb);
+    else
+        k_field<false><<<grid, TB * wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0],
+                                                 ax, ay, phi, bpw, wpb);
+}
+
+}  // namespace bh

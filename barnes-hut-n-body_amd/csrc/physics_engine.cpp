@@ -224,4 +224,20 @@ bh_diagnostics PhysicsEngine::diagnostics(bool potential) {
     return d;
 }
 
+void PhysicsEngine::computeField(const std::vector<double> &px, const std::vector<double> &py,
+                                 const std::vector<double> &pm, std::vector<double> &ax,
+                                 std::vector<double> &ay, std::vector<double> &phi) {
+    if (px.size() != py.size() || (!pm.empty() && pm.size() != px.size()))
+        throw std::runtime_error("computeField: px, py (and pm, unless empty) differ in size");
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    const size_t n = px.size();
+    ax.assign(n, 0.0);
+    ay.assign(n, 0.0);
+    phi.assign(n, 0.0);
+    check(bh_compute_field(eng_, (int64_t)n, px.data(), py.data(), pm.empty() ? nullptr : pm.data(),
+                           ax.data(), ay.data(), phi.data()));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+}
+
 }  // namespace bh

@@ -80,6 +80,13 @@ public:
     // counterpart).  potential = true builds a tree as step()'s first half does -- its jitter is
     // written back into the list -- and adds the potential energy; false only reads the state.
     bh_diagnostics diagnostics(bool potential = true);
+    // The field of the caller's list at probe points that are not bodies of it (bh_compute_field;
+    // no reference counterpart): ax, ay = F / pm and phi are resized to px.size(), probe order.
+    // pm empty: every probe has mass 1.0 (the field per unit mass).  Builds a tree as step()'s
+    // first half does -- its jitter is written back into the list; the probes never enter it.
+    void computeField(const std::vector<double> &px, const std::vector<double> &py,
+                      const std::vector<double> &pm, std::vector<double> &ax,
+                      std::vector<double> &ay, std::vector<double> &phi);
 
     double mergeMaxMass = 4000.0;        // BHA:315
     double mergeMinDist = Config::MIN_R; // BHA:321

@@ -745,7 +745,7 @@ uint32_t bodies_per_wave(int64_t lanes) {
 #ifndef BH_TRAV_WPB_FULL_WAVES
 #define BH_TRAV_WPB_FULL_WAVES 8192
 #endif
-static uint32_t waves_per_group(uint32_t waves, uint32_t bpw) {
+uint32_t waves_per_group(uint32_t waves, uint32_t bpw) {
     if (bpw < TB) return 1u;  // (short walks of a few bodies: C1 +1.5 % with 2)
     return waves >= BH_TRAV_WPB_FULL_WAVES ? 4u : waves >= 1024 ? 8u : 1u;
 }

@@ -199,7 +199,7 @@ int bh_step(bh_engine *e, int32_t k);
  * caller may only read the mirror it mapped before (bh_map_bodies: the call writes the other
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
- * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_compute_field, bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is.
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
@@ -288,6 +288,43 @@ int bh_compute_diagnostics(bh_engine *e, int with_potential, bh_diagnostics *out
 /* HIP-event duration (ms) of the last potential kernel launch (bh_compute_potential, or
  * bh_compute_diagnostics with the potential); 0 before the first. */
 int bh_potential_kernel_ms(const bh_engine *e, double *ms);
+
+/* The field of the current state at n_probe points that are not bodies of it: acceleration and
+ * potential at (px[j], py[j]).  The tree and the state semantics are exactly
+ * bh_compute_potential's: buildTree() as the first half of step() does it (the jitter's position
+ * mutation included), or the tree the previous call carried; always a full build on this engine,
+ * never a locally essential tree, not sharded; a tree-flag error is returned the same way; on a
+ * multi-device handle every member builds and member 0 evaluates and answers.  The probes never
+ * enter the engine's state, its caller-order bookkeeping or its mirror: the call leaves what
+ * bh_compute_accelerations would leave.
+ * Probe j is a Body(px[j], py[j], 0, 0, pm[j]) that is not in the tree; pm = NULL gives every
+ * probe mass 1.0, and (ax, ay) is then the field per unit mass (G * 1.0 and / 1.0 are exact).
+ * It visits the nodes accumulateForce visits for such a body (BHA:215-239): mass-0 nodes are
+ * skipped, EVERY non-empty leaf is taken -- nothing is skipped by identity, so a probe that sits
+ * on a body gets that body's full term, m / sqrt(soft2) in the potential -- and an internal node
+ * is taken iff s2 < theta^2 * dist2 (strict).  Every taken node, in pre-order, adds
+ *     dx = comX - px;  dy = comY - py;  r2 = dx*dx + dy*dy + soft2
+ *     invR = 1.0 / sqrt(r2);  invR2 = 1.0 / r2        (IEEE sqrt and divide, no contraction)
+ *     f = G * pm * m * invR2                          (left to right, BHA:256)
+ *     fx += f * dx * invR;  fy += f * dy * invR;  s += m * invR           (all from +0.0)
+ * and ax = fx / pm, ay = fy / pm (BHA:390-391), phi = -(G * s): bit-reproducible, no
+ * floating-point atomics, two calls with the same probes on the same state return identical
+ * bits.  Nothing special-cases odd inputs -- the result is what this arithmetic gives: pm = 0
+ * gives NaN accelerations and a valid phi, a probe on a centre of mass at soft2 = 0 gives NaN and
+ * -inf, a NaN coordinate gives NaN.  Probes outside the root cell, far outside it or non-finite
+ * are walked like any other.  With no body in the tree every sum stays +0.0 (phi = -0.0).
+ * theta = 0 goes through the same walk, which then opens every node: O(n_probe x nodes); there is
+ * no tiled all-pairs kernel for probes.
+ * ax, ay, phi (each nullable) have length n_probe, in the caller's probe order.  n_probe = 0
+ * returns BH_OK after the build, launches nothing and leaves bh_field_kernel_ms as it was.
+ * BH_E_INVALID (with bh_last_error text): e NULL, n_probe < 0 or > 2^28, px or py NULL with
+ * n_probe > 0. */
+int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const double *py,
+                     const double *pm, double *ax, double *ay, double *phi);
+
+/* HIP-event duration (ms) of the last field kernel launch (bh_compute_field; the probes' keying,
+ * sort and upload are outside it); 0 before the first. */
+int bh_field_kernel_ms(const bh_engine *e, double *ms);
 
 /* The body pass of a frame, rasterised on the device: what NBodyPanel.paintComponent's loop over
  * engine.getBodies() paints (PNL:302-307) -- one pixel per body, black if m >= 1000 (PNL:303),
