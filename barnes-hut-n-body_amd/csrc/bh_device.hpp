@@ -98,8 +98,12 @@ __host__ __device__ inline uint64_t sentinel_key(int J) { return 1ull << (2 * J)
 __host__ __device__ inline int key32_shift(int J) { return 2 * J + 1 > 32 ? 2 * J + 1 - 32 : 0; }
 
 // Force-evaluation constants (BHA:225,253,256,378).
+// thr0: the root's opening threshold on dist2 for (Geometry::s2[0], theta2), open_threshold.hpp
+// (force_params() in engine.cpp); 0.0 -- also what an initialiser without it leaves -- sends the
+// traversal down its IEEE walk.
 struct ForceParams {
     double G, soft2, theta2;
+    double thr0;
 };
 
 // Body state in slot order.

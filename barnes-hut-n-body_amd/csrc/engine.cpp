@@ -38,6 +38,7 @@
 #include "bh_device.hpp"
 #include "bh_engine.h"
 #include "multi.hpp"
+#include "open_threshold.hpp"
 #include "render_quads.hpp"
 #include "render_view.hpp"
 
@@ -855,6 +856,13 @@ int collect_timings(bh_engine *e) {
 // builds, the snapshot) asks this, so that it never disagrees with the kernel choice.
 bool theta2_is_zero(const bh_engine *e) { return e->p.theta * e->p.theta == 0.0; }
 
+// The force-evaluation constants (BHA:378) of the engine's parameters, with the root's opening
+// threshold for its geometry (open_threshold.hpp): the one place every evaluation gets them.
+ForceParams force_params(const bh_engine *e) {
+    const double theta2 = e->p.theta * e->p.theta;
+    return ForceParams{e->p.G, e->p.soft2, theta2, open_threshold(e->geo.s2[0], theta2)};
+}
+
 // What one build is asked for (build_into), and what it did.
 struct BuildRequest {
     // the pipelined step's next tree, built on stream `s` beside the second traversal into
@@ -1445,7 +1453,7 @@ int evaluate_let(bh_engine *e, KickMode kick, bool *done) {
         }
     }
     TRY(mark(e, 0));
-    const ForceParams fp{e->p.G, e->p.soft2, e->p.theta * e->p.theta};
+    const ForceParams fp = force_params(e);
     const int W = 2;  // (x, y) per lane
     KickArgs ka{kick == KICK_DRIFT ? KICK_OWN_DRIFT : KICK_OWN_ONLY, e->st.vx, e->st.vy,
                 e->p.dt * 0.5, e->p.dt, lanes};  // BHA:412
@@ -1641,7 +1649,7 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
         }
         TRY(mark(e, 0));
     }
-    ForceParams fp{e->p.G, e->p.soft2, e->p.theta * e->p.theta};  // BHA:378
+    ForceParams fp = force_params(e);  // BHA:378
     const uint32_t *d_T = e->base + n;
     if (pot) {  // the potential on this tree, by this engine alone, over the whole list
         if (!pot->run) return BH_OK;
@@ -2338,7 +2346,7 @@ int evaluate_pipelined(bh_engine *e, bool last) {
         HIPCHK(e, hipEventRecord(e->pipe_ev[0], s));
         HIPCHK(e, hipStreamWaitEvent(e->pipe_stream, e->pipe_ev[0], 0));
     }
-    const ForceParams fp{e->p.G, e->p.soft2, e->p.theta * e->p.theta};  // BHA:378
+    const ForceParams fp = force_params(e);  // BHA:378
     KickArgs ka{KICK_ONLY, e->st.vx, e->st.vy, e->p.dt * 0.5, e->p.dt};
     if (n > 0) {  // (the build swapped: the previous order's velocities are in alt)
         ka.svx = e->alt.vx;
@@ -3804,7 +3812,7 @@ static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay,
         SYNC(e, e->stream);
         TRY(check_tree_flags(e));
     } else if (run) {  // no bodies, no tree: every sum stays +0.0
-        const ForceParams fp{e->p.G, e->p.soft2, e->p.theta * e->p.theta};
+        const ForceParams fp = force_params(e);
         TRY(field_launch(e, fe, nullptr, 0, nullptr, fp));
         SYNC(e, e->stream);
     }

@@ -92,7 +92,8 @@ __device__ __forceinline__ bool lane_self_ok(double Gm, double bm) {
     return __builtin_fabs(Gm * bm) < 0x1p400;
 }
 
-// The fast criterion forms s2 = s2_0 * 2^-2d by an exponent-field subtraction (traverse.hip):
+// The fast criterion forms s2 = s2_0 * 2^-2d by an exponent-field subtraction (potential.hip,
+// field.hip; traverse.hip scales its threshold on dist2 the same way, open_threshold.hpp):
 // exact while the result stays normal, i.e. for every 2d <= 255 (NODE_DEPTH2_MASK) when
 // s2_0 >= 2^-760; finite s2_0 only.
 __device__ __forceinline__ bool fast_s2_ok(double s2root) {

@@ -19,6 +19,7 @@
 // per wave and examines the tree level by level, the terms added in pre-order -- the same sum.
 #include "bh_device.hpp"
 #include "fastmath.hpp"
+#include "open_threshold.hpp"
 
 namespace bh {
 namespace {
@@ -80,8 +81,8 @@ __device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
 template <bool FAST, bool COUNT, bool OFF32>
 __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T, double bx,
                                      double by, double Gm, double soft2, double theta2,
-                                     double s2root, uint32_t self, uint32_t resume, double &fx,
-                                     double &fy, uint32_t &nvis, uint32_t &niters,
+                                     double s2root, double thr0, uint32_t self, uint32_t resume,
+                                     double &fx, double &fy, uint32_t &nvis, uint32_t &niters,
                                      uint32_t &ncontrib, uint32_t &nblocks) {
     uint32_t cur = 0;
     // one iteration on record `rec`; the next record is requested into `nrec`.  The loop body
@@ -114,29 +115,35 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
         const double dy = comY - by;
         const double d2 = dx * dx + dy * dy + soft2;
         uint64_t contrib_m, open_m;  // lanes that take / open this node
-        if (meta & NODE_LEAF) {  // BHA:217-221: skip self by identity
-            // fast path: the own leaf's term is an exact +-0 (fastmath.hpp, lane_self_ok)
-            contrib_m = FAST ? act_m
-                             : act_m & __builtin_amdgcn_ballot_w64((meta & NODE_BODY_MASK) != self);
+        if (FAST) {
+            // One compare for leaves and internal nodes alike (open_threshold.hpp): a lane accepts
+            // the node iff d2 >= thr0 * 2^-2d -- the reference's s2 < theta2 * d2 (BHA:226-228)
+            // restated, exact under open_threshold_ok -- with the threshold built on the scalar
+            // unit by subtracting 2d from thr0's exponent field.  A leaf (BHA:217-221), or a
+            // massless cell that carries the leaf flag, has a threshold no d2 is below: every lane
+            // accepts it, so contrib_m = act_m and open_m = 0; the own leaf's term is an exact +-0
+            // (fastmath.hpp, lane_self_ok).  No product by theta2, no leaf / internal branch.
+            // Only the high word is computed and selected: the leaf's threshold keeps thr0's low
+            // word under a zero exponent field, a subnormal -- below every d2 >= soft2 >= 2^-600
+            // just as +0.0 is (one scalar instruction less per stop than the 64-bit select).
+            const uint64_t t0 = (uint64_t)__double_as_longlong(thr0);
+            const uint32_t thi = (uint32_t)(t0 >> 32) - ((meta & NODE_DEPTH2_MASK) << 20);
+            typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));  // (a register pair, no OR)
+            const u32x2 tw = {(uint32_t)t0, (meta & NODE_LEAF) ? 0u : thi};
+            const double thr = __builtin_bit_cast(double, tw);
+            const uint64_t acc_m = __builtin_amdgcn_ballot_w64(d2 >= thr);
+            contrib_m = act_m & acc_m;
+            open_m = act_m & ~acc_m;
+        } else if (meta & NODE_LEAF) {  // BHA:217-221: skip self by identity
+            contrib_m = act_m & __builtin_amdgcn_ballot_w64((meta & NODE_BODY_MASK) != self);
             open_m = 0;
         } else {
             // s2 = (h_d * 2.0)^2 with h_d = h_0 / 2^d exactly, so s2 = s2_0 * 4^-d exactly
             // (a power-of-two scaling commutes with rounding), and s2 < t2 <=> s2_0 < t2 * 4^d:
             // the scaling of t2 is exact too (up from a subnormal included) or overflows to
             // +inf where s2 < t2 holds anyway.  The record carries 2d: one scalar mask.
-            // Fast path: s2 itself, the reference's own comparison, built on the scalar unit by
-            // subtracting 2d from s2_0's exponent field (exact: s2_0 >= 2^-760 keeps it normal
-            // for every 2d <= 255, fast_s2_ok) -- one v_ldexp_f64 less per internal node.
-            uint64_t acc_m;
-            if (FAST) {
-                const uint64_t s2b = (uint64_t)__double_as_longlong(s2root) -
-                                     ((uint64_t)(meta & NODE_DEPTH2_MASK) << 52);
-                acc_m = __builtin_amdgcn_ballot_w64(__longlong_as_double((long long)s2b) <
-                                                    theta2 * d2);  // BHA:226-228
-            } else {
-                const double t2 = __builtin_ldexp(theta2 * d2, (int)(meta & NODE_DEPTH2_MASK));
-                acc_m = __builtin_amdgcn_ballot_w64(s2root < t2);  // BHA:226-228
-            }
+            const double t2 = __builtin_ldexp(theta2 * d2, (int)(meta & NODE_DEPTH2_MASK));
+            const uint64_t acc_m = __builtin_amdgcn_ballot_w64(s2root < t2);  // BHA:226-228
             contrib_m = act_m & acc_m;
             open_m = act_m & ~acc_m;
         }
@@ -250,8 +257,8 @@ __device__ uint64_t g_bfs_times[BFS_T_W * BFS_T_REC];
 
 // false: a buffer overflowed (the caller walks the body with walk()).  fx, fy: wave-uniform.
 __device__ bool bfs_walk(const Node *__restrict__ nodes, uint32_t T,
-                         double bx, double by, double Gm, double soft2, double theta2,
-                         double s2root, uint32_t *lds, uint32_t bm_words, double &fx, double &fy) {
+                         double bx, double by, double Gm, double soft2, double thr0,
+                         uint32_t *lds, uint32_t bm_words, double &fx, double &fy) {
     const uint32_t lane = threadIdx.x & 63u;
     fx = 0.0;
     fy = 0.0;
@@ -270,9 +277,9 @@ __device__ bool bfs_walk(const Node *__restrict__ nodes, uint32_t T,
         if (r.meta & NODE_LEAF) return false;  // (massless cells carry the leaf flag too)
         const double dx = r.comX - bx, dy = r.comY - by;
         const double d2 = dx * dx + dy * dy + soft2;
-        const uint64_t s2b = (uint64_t)__double_as_longlong(s2root) -
-                             ((uint64_t)(r.meta & NODE_DEPTH2_MASK) << 52);
-        return !(__longlong_as_double((long long)s2b) < theta2 * d2);
+        const uint64_t thrb = (uint64_t)__double_as_longlong(thr0) -
+                              ((uint64_t)(r.meta & NODE_DEPTH2_MASK) << 52);
+        return !(d2 >= __longlong_as_double((long long)thrb));  // walk<true>'s comparison
     };
     uint32_t nE = 0;
     {
@@ -480,13 +487,14 @@ __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_s
     // lane is active for node `cur` iff cur >= resume; invalid lanes and tombstones never are.
     const uint32_t resume = walks ? 0u : 0xFFFFFFFFu;
     const uint32_t T = __builtin_amdgcn_readfirstlane(*d_T);
-    const bool fast = fast_s2_ok(s2root) &&
+    const double thr0 = fp.thr0;
+    const bool fast = fast_s2_ok(s2root) && open_threshold_ok(thr0, theta2) &&
         __ballot(walks && !(lane_fast_ok(bx, by, soft2) && lane_self_ok(Gm, bm))) == 0ull;
     bool walked = false;
     if (BFS && fast && (__ballot(walks) & 1ull)) {  // one body per wave: lane 0's (bpw == 1)
         double ux, uy;
-        walked = bfs_walk(nodes, T, rfl_f64(bx), rfl_f64(by), rfl_f64(Gm), soft2, theta2, s2root,
-                          lds, bm_words, ux, uy);
+        walked = bfs_walk(nodes, T, rfl_f64(bx), rfl_f64(by), rfl_f64(Gm), soft2, thr0, lds,
+                          bm_words, ux, uy);
         if (walked) {
             fx = ux;
             fy = uy;
@@ -494,11 +502,11 @@ __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_s
     }
     if (walked) {
     } else if (fast)
-        walk<true, COUNT, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, self, resume, fx,
-                                 fy, nvis, niters, ncontrib, nblocks);
+        walk<true, COUNT, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, thr0, self, resume,
+                                 fx, fy, nvis, niters, ncontrib, nblocks);
     else
-        walk<false, COUNT, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, self, resume, fx,
-                                  fy, nvis, niters, ncontrib, nblocks);
+        walk<false, COUNT, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, thr0, self, resume,
+                                  fx, fy, nvis, niters, ncontrib, nblocks);
     if (wo.cost && lane == 0 && q < hi)
         wo.cost[v] = (uint32_t)(wall_clock64() - t_start < 0xFFFFFFull
                                     ? wall_clock64() - t_start : 0xFFFFFFull);
@@ -615,12 +623,46 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
 // squares of random doubles +- a few ulp (sqrt ties region); the physical range [1, 2^24).
 constexpr int STB = 256;  // self-test block
 
-__global__ __launch_bounds__(STB) void k_selftest_math(int64_t n, uint64_t seed,
+// The criterion's two forms (walk<true>'s threshold compare against the product form it replaced,
+// the reference's own comparison on s2_d) on the first THR_OPS operands: (s2_0, theta2) pair
+// i % THR_PAIRS, 2d = every even value up to 254, and d2 at the scaled threshold, +-1 and +-2 ulp
+// around it, or random across the fast path's [2^-600, 2^67].
+constexpr int THR_PAIRS = 12;
+constexpr int64_t THR_OPS = int64_t(1) << 26;
+struct ThrCases {
+    double s2[THR_PAIRS], theta2[THR_PAIRS], thr0[THR_PAIRS];
+};
+
+__device__ __forceinline__ uint32_t selftest_criterion(const ThrCases &tc, int64_t i, uint64_t r0,
+                                                       uint64_t r1) {
+    const int pair = (int)(i % THR_PAIRS);
+    const uint32_t k = (uint32_t)((i / THR_PAIRS) % 128) * 2u;  // 2d
+    const double s2_0 = tc.s2[pair], theta2 = tc.theta2[pair], thr0 = tc.thr0[pair];
+    if (!(fast_s2_ok(s2_0) && open_threshold_ok(thr0, theta2))) return 0;
+    const uint64_t thrb = (uint64_t)__double_as_longlong(thr0) - ((uint64_t)k << 52);
+    const uint32_t kind = (uint32_t)(r1 >> 40) % 6u;  // 0..4: threshold - 2 .. + 2 ulp, 5: random
+    double d2;
+    if (kind < 5) {
+        d2 = __longlong_as_double((long long)(thrb + kind) - 2);
+    } else {
+        const int ex = (int)(r0 % 668) - 600;  // [-600, 67]
+        d2 = __builtin_ldexp(
+            __longlong_as_double((long long)((1023ull << 52) | (r1 & ((1ull << 52) - 1)))), ex);
+    }
+    if (!(d2 >= 0x1p-600 && d2 <= 0x1p67)) return 0;
+    const uint64_t s2b = (uint64_t)__double_as_longlong(s2_0) - ((uint64_t)k << 52);
+    const bool was = __longlong_as_double((long long)s2b) < theta2 * d2;  // BHA:226-228
+    const bool now = d2 >= __longlong_as_double((long long)thrb);
+    return was != now ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(STB) void k_selftest_math(int64_t n, uint64_t seed, ThrCases tc,
                                                       unsigned long long *bad) {
     uint32_t local = 0;
     for (int64_t i = (int64_t)blockIdx.x * STB + threadIdx.x; i < n;
          i += (int64_t)gridDim.x * STB) {
         const uint64_t r0 = mix64(seed ^ (uint64_t)i), r1 = mix64(r0);
+        if (i < THR_OPS) local += selftest_criterion(tc, i, r0, r1);
         const int kind = (int)(r1 >> 62);
         uint64_t mant = r0 & ((1ull << 52) - 1);
         int ex = (int)(r1 % 1104) - 600;  // [-600, 503]
@@ -708,7 +750,19 @@ hipError_t wave_order(const uint32_t *cost, int64_t n, uint32_t *order, hipStrea
 }
 
 hipError_t selftest_fast_math(int64_t n, uint64_t seed, unsigned long long *d_bad, hipStream_t s) {
-    k_selftest_math<<<4096, STB, 0, s>>>(n, seed, d_bad);
+    // the criterion's cases: root cells of 1000, 1920, 100 and 3 pixels (s2_0 = (2 h_0)^2 with
+    // h_0 = max(W, H) / 2 + 2), theta a power of two or not, thr0 by the engine's own function
+    static const double roots[THR_PAIRS] = {1004.0, 1004.0, 1004.0, 1004.0, 1004.0, 1004.0,
+                                            1924.0, 1924.0, 104.0,  104.0,  7.0,    7.0};
+    static const double thetas[THR_PAIRS] = {0.5, 0.3,  0.75, 1.0,  1.6,         0.123456789,
+                                             0.5, 0.7071067811865476, 0.25, 1e-3, 2.0, 0.3};
+    ThrCases tc;
+    for (int j = 0; j < THR_PAIRS; ++j) {
+        tc.s2[j] = roots[j] * roots[j];
+        tc.theta2[j] = thetas[j] * thetas[j];
+        tc.thr0[j] = open_threshold(tc.s2[j], tc.theta2[j]);
+    }
+    k_selftest_math<<<4096, STB, 0, s>>>(n, seed, tc, d_bad);
     return hipGetLastError();
 }
 

@@ -504,6 +504,9 @@ int bh_launch_plan(const bh_params *p, int64_t n, int64_t *out, int64_t cap, int
 /* Diagnostic: checks, on HIP device `device`, the traversal's reduced-range exact sequences
  * for sqrt(d2), 1/sqrt(d2) and 1/d2 (traverse.hip) bit-for-bit against the IEEE operations on
  * n generated operands (random, near powers of two, near perfect squares, physical range);
+ * on the first 2^26 of them it also evaluates the walk's opening criterion in its two forms
+ * (s2 < theta^2 * d2 and d2 >= threshold) for several root cells and theta, every depth, d2 at
+ * the threshold +- 2 ulp and random, and counts disagreements into the same number;
  * *mismatches receives the number of differing results (0 expected). */
 int bh_selftest_fast_math(int device, int64_t n, uint64_t seed, int64_t *mismatches);
 
