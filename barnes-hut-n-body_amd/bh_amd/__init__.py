@@ -51,6 +51,8 @@ EXPORTED_SYMBOLS = (
     "bh_nbody3d_center_of_mass", "bh_default_view", "bh_render_bodies", "bh_render_kernel_ms",
     "bh_launch_plan", "bh_render_quads", "bh_render_quads_kernel_ms",
     "bh_compute_field", "bh_field_kernel_ms",
+    "bh_compute_field_direct", "bh_compute_force_error", "bh_direct_field_kernel_ms",
+    "bh_direct_field_shape",
 )
 
 
@@ -81,6 +83,35 @@ class BhDiagnostics(ctypes.Structure):
         ("kinetic", ctypes.c_double),
         ("potential", ctypes.c_double),
     ]
+
+
+class BhForceError(ctypes.Structure):
+    """struct bh_force_error (include/bh_engine.h) -- the summary of bh_compute_force_error."""
+    _fields_ = [
+        ("n_sample", ctypes.c_int64),
+        ("n_used", ctypes.c_int64),
+        ("worst", ctypes.c_int64),
+        ("max_rel", ctypes.c_double),
+        ("mean_rel", ctypes.c_double),
+        ("rms_rel", ctypes.c_double),
+    ]
+
+
+@dataclass(frozen=True)
+class ForceError:
+    """Engine.force_error(): the sampled bodies' tree and exact accelerations and the summary of
+    |a_tree - a_exact| / |a_exact| over the samples that are finite with |a_exact| > 0."""
+    idx: np.ndarray
+    ax_tree: np.ndarray
+    ay_tree: np.ndarray
+    ax_exact: np.ndarray
+    ay_exact: np.ndarray
+    n_sample: int
+    n_used: int
+    worst: int  # position in idx of max_rel (the first on ties); -1 if n_used == 0
+    max_rel: float
+    mean_rel: float
+    rms_rel: float
 
 
 class BhView(ctypes.Structure):
@@ -195,6 +226,11 @@ def load_library(path: str | None = None):
     lib.bh_potential_kernel_ms.argtypes = [_VP, _D]
     lib.bh_compute_field.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
     lib.bh_field_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_compute_field_direct.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
+    lib.bh_compute_force_error.argtypes = [_VP, ctypes.c_int64, _I64P, _D, _D, _D, _D,
+                                           ctypes.POINTER(BhForceError)]
+    lib.bh_direct_field_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_direct_field_shape.argtypes = [ctypes.c_int64, _I64P]
     lib.bh_default_view.argtypes = [ctypes.POINTER(BhView)]
     lib.bh_default_view.restype = None
     lib.bh_render_bodies.argtypes = [_VP, ctypes.POINTER(BhView), ctypes.POINTER(ctypes.c_uint8),
@@ -320,6 +356,17 @@ def launch_plan(n: int, params: BhParams | None = None) -> dict:
     if got.value != out.size:
         raise BhError(BH_E_INVALID, "bh_launch_plan: field list out of date")
     return {k: int(v) for k, v in zip(LAUNCH_PLAN_FIELDS, out)}
+
+
+def direct_field_shape(n: int):
+    """(leaf records per LDS tile, lanes per workgroup, targets per lane) of the all-pairs kernel
+    behind compute_field_direct and force_error for `n` targets (bh_direct_field_shape;
+    host-only, no device)."""
+    out = np.zeros(3, dtype=np.int64)
+    rc = load_library().bh_direct_field_shape(int(n), out.ctypes.data_as(_I64P))
+    if rc != BH_OK:
+        raise BhError(rc, "bh_direct_field_shape: invalid arguments")
+    return int(out[0]), int(out[1]), int(out[2])
 
 
 class NBody3D:
@@ -663,6 +710,55 @@ class Engine:
         """HIP-event time (ms) of the last field kernel launch (bh_field_kernel_ms)."""
         ms = ctypes.c_double(0.0)
         self._check(self._lib.bh_field_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def compute_field_direct(self, px, py, pm=None, want_accel=True, want_phi=True):
+        """bh_compute_field_direct: compute_field with no cell ever accepted, whatever the
+        engine's theta -- every non-empty leaf is summed, by a tiled all-pairs kernel.  Same
+        arguments, results and state semantics; bit-identical to compute_field on an engine
+        that holds the same state with theta = 0."""
+        px = np.ascontiguousarray(px, dtype=np.float64)
+        py = np.ascontiguousarray(py, dtype=np.float64)
+        n = len(px)
+        if px.ndim != 1 or py.shape != px.shape:
+            raise ValueError("px and py must be 1-d arrays of equal length")
+        if pm is not None:
+            pm = np.ascontiguousarray(pm, dtype=np.float64)
+            if pm.shape != px.shape:
+                raise ValueError("pm must have the length of px")
+        ax = np.empty(n, dtype=np.float64) if want_accel else None
+        ay = np.empty(n, dtype=np.float64) if want_accel else None
+        phi = np.empty(n, dtype=np.float64) if want_phi else None
+        self._check(self._lib.bh_compute_field_direct(self._h, n, _dp(px), _dp(py), _dp(pm),
+                                                      _dp(ax), _dp(ay), _dp(phi)))
+        return ax, ay, phi
+
+    def force_error(self, idx=None, sample=4096, seed=0) -> ForceError:
+        """bh_compute_force_error: the tree's accelerations of sampled bodies at the engine's
+        theta beside their exact (theta = 0) ones, from one build, and the summary of the
+        relative error.  idx: indices into the list get_bodies() returns (any order, duplicates
+        allowed); None draws min(sample, N) distinct ones with np.random.default_rng(seed),
+        sorted.  State semantics of compute_accelerations."""
+        if idx is None:
+            n = max(self.num_bodies(), 0)
+            idx = np.sort(np.random.default_rng(seed).choice(n, min(int(sample), n),
+                                                             replace=False))
+        idx = np.ascontiguousarray(idx, dtype=np.int64)
+        if idx.ndim != 1:
+            raise ValueError("idx must be a 1-d array")
+        k = len(idx)
+        out = [np.empty(k, dtype=np.float64) for _ in range(4)]
+        s = BhForceError()
+        self._check(self._lib.bh_compute_force_error(
+            self._h, k, idx.ctypes.data_as(_I64P), *[_dp(a) for a in out], ctypes.byref(s)))
+        return ForceError(idx, *out, int(s.n_sample), int(s.n_used), int(s.worst), s.max_rel,
+                          s.mean_rel, s.rms_rel)
+
+    def direct_field_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last all-pairs kernel launch of compute_field_direct or
+        force_error (bh_direct_field_kernel_ms)."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.bh_direct_field_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
     def render_bodies(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,

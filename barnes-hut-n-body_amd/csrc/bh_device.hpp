@@ -609,6 +609,32 @@ void direct_potential(const LeafList &L, const uint32_t *d_count, const double *
                       const uint32_t *cidx, int64_t n, double G, double soft2, double *phi,
                       hipStream_t s);
 
+// ---- launchers (direct_field.hip): the leaf sequence summed for a list of targets --------
+// What direct_targets launches for n_target targets (host-only; direct_targets itself launches
+// from it, and bh_direct_field_shape reports it).
+struct DirectFieldShape {
+    int tile;      // leaf records staged in LDS per tile
+    int lanes;     // lanes per workgroup
+    int per_lane;  // targets per lane
+};
+DirectFieldShape direct_field_shape(int64_t n_target);
+// Target j = (tx[j], ty[j]) of mass tm[j] (tm null: 1.0) takes every leaf of the sequence in
+// order -- but, with tslot, the leaf of body slot tslot[j] (a body of the state; 0xFFFFFFFF or a
+// slot without a leaf: nothing is skipped) -- and gets ax[j], ay[j] = F / tm and, without tslot,
+// phi[j] = -(G * sum of m / sqrt(dist2 + soft2)) (with tslot phi is not written).  Bit-identical
+// to field_walk (no tslot) and to direct_forces (tslot) with theta2 = 0 on the same tree.
+// d_count null: no tree, every sum stays +0.0.
+void direct_targets(const LeafList &L, const uint32_t *d_count, const double *tx, const double *ty,
+                    const double *tm, const uint32_t *tslot, int64_t n, double G, double soft2,
+                    double *ax, double *ay, double *phi, hipStream_t s);
+// The targets of bh_compute_force_error: sample j < k is the body at caller index idx[j] (< n) of
+// the state st -- its x, y, m and slot, and its acceleration (ax_c, ay_c: caller order, n
+// entries) gathered into ax_tree, ay_tree.  slot_of: n entries of scratch.
+hipError_t direct_body_targets(int64_t n, const BodyState &st, const uint32_t *idx, int64_t k,
+                               uint32_t *slot_of, const double *ax_c, const double *ay_c,
+                               double *tx, double *ty, double *tm, uint32_t *tslot,
+                               double *ax_tree, double *ay_tree, hipStream_t s);
+
 // ---- launchers (potential.hip) ---------------------------------------------------
 // phi[p] = -(G * sum of mass / sqrt(dist2 + soft2)) over the nodes body p's force walk takes
 // (BHA:215-239: massless nodes skipped, the own leaf skipped by identity, an internal node taken

@@ -236,6 +236,16 @@ struct bh_engine {
     hipEvent_t fld_ev[2] = {nullptr, nullptr};  // around the last field kernel
     bool fld_timed = false;
 
+    // bh_compute_field_direct / bh_compute_force_error (direct_field.hip): the targets' buffers,
+    // the calls' own as bh_compute_field's are, allocated on first use and grown when needed
+    double *dfl_in = nullptr;         // tx, ty, tm planes of dfl_cap targets
+    double *dfl_out = nullptr;        // ax, ay, phi, ax_tree, ay_tree planes, by target index
+    uint32_t *dfl_u32 = nullptr;      // the samples' caller indices, their slots
+    uint32_t *dfl_slot_of = nullptr;  // caller index -> slot, dfl_slot_cap entries
+    int64_t dfl_cap = 0, dfl_slot_cap = 0;
+    hipEvent_t dfl_ev[2] = {nullptr, nullptr};  // around the last k_direct_targets launch
+    bool dfl_timed = false;
+
     // bh_render_bodies (render.hip): buffers of its own, allocated on first use, kept while the
     // padded pixel count is unchanged.  rnd_packed / rnd_cnt are zero between calls (the resolve
     // kernel re-zeroes what the rasteriser touched); rnd_clean = false: a call failed in between
@@ -1563,6 +1573,9 @@ struct FieldEval {
     bool run;
     int64_t n_probe;
     const double *px, *py, *pm;
+    // bh_compute_field_direct: every leaf of the tree's leaf sequence summed by the tiled kernel
+    // (direct_field.hip) into e->dfl_out, whatever theta is -- no cell is accepted
+    bool direct = false;
 };
 
 int field_bufs(bh_engine *e, int64_t n_probe) {
@@ -1603,6 +1616,41 @@ int field_launch(bh_engine *e, const FieldEval &f, const Node *nodes, size_t nod
     HIPCHK(e, hipGetLastError());
     HIPCHK(e, hipEventRecord(e->fld_ev[1], e->stream));
     e->fld_timed = true;
+    return BH_OK;
+}
+
+int direct_field_bufs(bh_engine *e, int64_t n_target) {
+    if (n_target > e->dfl_cap || !e->dfl_in) {
+        const size_t cap = (size_t)n_target;
+        e->dfl_cap = 0;
+        TRY(dev_alloc(e, e->dfl_in, 3 * cap));
+        TRY(dev_alloc(e, e->dfl_out, 5 * cap));
+        TRY(dev_alloc(e, e->dfl_u32, 2 * cap));
+        e->dfl_cap = n_target;
+    }
+    for (hipEvent_t &ev : e->dfl_ev)
+        if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return BH_OK;
+}
+
+// Upload the probes, then k_direct_targets between its two events.  tree: the leaf sequence of
+// the engine's tree was just extracted (ensure_direct + leaf_list_build); else there is no tree
+// (no bodies) and every sum stays +0.0.
+int direct_field_launch(bh_engine *e, const FieldEval &f, bool tree, const ForceParams &fp) {
+    const int64_t P = f.n_probe;
+    TRY(direct_field_bufs(e, P));
+    const size_t cap = (size_t)e->dfl_cap, bytes = sizeof(double) * (size_t)P;
+    double *px = e->dfl_in, *py = px + cap, *pm = f.pm ? py + cap : nullptr;
+    HIPCHK(e, hipMemcpyAsync(px, f.px, bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(py, f.py, bytes, hipMemcpyHostToDevice, e->stream));
+    if (pm) HIPCHK(e, hipMemcpyAsync(pm, f.pm, bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipEventRecord(e->dfl_ev[0], e->stream));
+    direct_targets(tree ? e->leaves : LeafList{nullptr}, tree ? e->leaf_count : nullptr, px, py, pm,
+                   nullptr, P, fp.G, fp.soft2, e->dfl_out, e->dfl_out + cap, e->dfl_out + 2 * cap,
+                   e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->dfl_ev[1], e->stream));
+    e->dfl_timed = true;
     return BH_OK;
 }
 
@@ -1675,6 +1723,13 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
     if (fld) {  // the field at the probes on this tree, by this engine alone (theta = 0: the
                 // same walk, which then opens every internal node)
         if (!fld->run || fld->n_probe == 0) return BH_OK;
+        if (fld->direct) {  // every leaf, by the tiled kernel (direct_field.hip)
+            TRY(ensure_direct(e));
+            HIPCHK(e, leaf_list_build(e->nodes, d_T, (int64_t)e->node_cap, e->leaf_flags,
+                                      e->leaf_sel, e->leaf_count, e->leaves, n, e->leaf_cover,
+                                      e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
+            return direct_field_launch(e, *fld, true, fp);
+        }
         return field_launch(e, *fld, e->nodes, e->node_cap, d_T, fp);
     }
     const bool direct = fp.theta2 == 0.0 && !visits;
@@ -3141,12 +3196,15 @@ void bh_destroy(bh_engine *e) {
                     e->mir_keep, e->mir_pos, e->mir_tmp, e->mir_idx_stage, e->lanes_next, e->lr_hkey, e->lr_hkey_s,
                     e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
-                    e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch};
+                    e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch,
+                    e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (hipEvent_t ev : e->pot_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->fld_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (hipEvent_t ev : e->dfl_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->rnd_ev)
         if (ev) (void)hipEventDestroy(ev);
@@ -3813,15 +3871,19 @@ static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay,
         TRY(check_tree_flags(e));
     } else if (run) {  // no bodies, no tree: every sum stays +0.0
         const ForceParams fp = force_params(e);
-        TRY(field_launch(e, fe, nullptr, 0, nullptr, fp));
+        if (fe.direct)
+            TRY(direct_field_launch(e, fe, false, fp));
+        else
+            TRY(field_launch(e, fe, nullptr, 0, nullptr, fp));
         SYNC(e, e->stream);
     }
     if (run) {
-        const size_t cap = (size_t)e->fld_cap, bytes = sizeof(double) * (size_t)P;
+        const size_t cap = (size_t)(fe.direct ? e->dfl_cap : e->fld_cap);
+        const size_t bytes = sizeof(double) * (size_t)P;
+        const double *res = fe.direct ? e->dfl_out : e->fld_out;
         double *out[3] = {ax, ay, phi};
         for (int k = 0; k < 3; ++k)
-            if (out[k])
-                HIPCHK(e, hipMemcpy(out[k], e->fld_out + k * cap, bytes, hipMemcpyDeviceToHost));
+            if (out[k]) HIPCHK(e, hipMemcpy(out[k], res + k * cap, bytes, hipMemcpyDeviceToHost));
     }
     if (e->profiling) TRY(collect_timings(e));
     return BH_OK;
@@ -3860,6 +3922,188 @@ int bh_field_kernel_ms(const bh_engine *e, double *ms) {
     float f = 0.f;
     if (hipEventElapsedTime(&f, e->fld_ev[0], e->fld_ev[1]) != hipSuccess) return BH_E_DEVICE;
     *ms = (double)f;
+    return BH_OK;
+}
+
+int bh_compute_field_direct(bh_engine *e, int64_t n_probe, const double *px, const double *py,
+                            const double *pm, double *ax, double *ay, double *phi) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (n_probe < 0 || n_probe > ((int64_t)1 << 28)) {
+        e->err = "bh_compute_field_direct: n_probe must be in [0, 2^28]";
+        return BH_E_INVALID;
+    }
+    if (n_probe > 0 && (!px || !py)) {
+        e->err = "bh_compute_field_direct: px or py is NULL";
+        return BH_E_INVALID;
+    }
+    const FieldEval all{true, n_probe, px, py, pm, true};
+    const FieldEval none{false, 0, nullptr, nullptr, nullptr, true};
+    // (every member builds, member 0 evaluates and answers: as bh_compute_field)
+    MULTI_ALL(e, r_ == 0 ? field_call(m_, all, ax, ay, phi)
+                         : field_call(m_, none, nullptr, nullptr, nullptr));
+    return field_call(e, all, ax, ay, phi);
+}
+
+// bh_compute_force_error's summary of the four sample arrays (include/bh_engine.h): sequential,
+// in sample order, binary64, nothing contracted.
+static void force_error_summary(int64_t k, const double *axt, const double *ayt, const double *axe,
+                                const double *aye, bh_force_error *out) {
+    *out = bh_force_error{};
+    out->n_sample = k;
+    out->worst = -1;
+    double sum = 0.0, sumsq = 0.0;
+    for (int64_t j = 0; j < k; ++j) {
+        if (!(std::isfinite(axt[j]) && std::isfinite(ayt[j]) && std::isfinite(axe[j]) &&
+              std::isfinite(aye[j])))
+            continue;
+        const double den = std::sqrt(axe[j] * axe[j] + aye[j] * aye[j]);
+        if (!(den > 0.0)) continue;
+        const double dx = axt[j] - axe[j], dy = ayt[j] - aye[j];
+        const double rel = std::sqrt(dx * dx + dy * dy) / den;
+        if (out->n_used == 0 || rel > out->max_rel) {  // the first on ties
+            out->max_rel = rel;
+            out->worst = j;
+        }
+        sum += rel;
+        sumsq += rel * rel;
+        ++out->n_used;
+    }
+    if (out->n_used > 0) {
+        out->mean_rel = sum / (double)out->n_used;
+        out->rms_rel = std::sqrt(sumsq / (double)out->n_used);
+    }
+}
+
+// What bh_compute_force_error asks of one engine.  run = false: the evaluation alone (the members
+// of a multi-device handle past the first).  idx: the validated caller indices.
+struct ForceErrorArgs {
+    bool run;
+    int64_t k;
+    const uint32_t *idx;
+    double *axt, *ayt, *axe, *aye;
+    bh_force_error *out;
+};
+
+// compute_accelerations_rank's evaluation, then -- on the same tree, in the same call -- the
+// samples' exact accelerations by k_direct_targets in body mode over the tree's leaf sequence.
+static int force_error_rank(bh_engine *e, const ForceErrorArgs &fa) {
+    e->prog_api.store(++e->api_calls);
+    HIPCHK(e, hipSetDevice(e->device));
+    const int64_t n = e->n, K = fa.k;
+    const bool run = fa.run && K > 0 && n > 0;  // (K > 0 with n = 0 was refused: no valid index)
+    e->ev_used = 0;
+    e->timings_pending = false;
+    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
+    if (n > 0) {
+        TRY(evaluate(e, nullptr));
+        e->mir_fresh = false;
+        scatter_acc_to_caller(n, e->st.cidx, e->a2, e->ax, e->ay, e->stream, e->a2_lanes,
+                              e->a2_layout);
+        HIPCHK(e, hipGetLastError());
+        if (run) {
+            const ForceParams fp = force_params(e);
+            TRY(ensure_direct(e));
+            HIPCHK(e, leaf_list_build(e->nodes, e->base + n, (int64_t)e->node_cap, e->leaf_flags,
+                                      e->leaf_sel, e->leaf_count, e->leaves, n, e->leaf_cover,
+                                      e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
+            TRY(direct_field_bufs(e, K));
+            if (e->dfl_slot_cap < n || !e->dfl_slot_of) {
+                e->dfl_slot_cap = 0;
+                TRY(dev_alloc(e, e->dfl_slot_of, (size_t)e->cap));
+                e->dfl_slot_cap = e->cap;
+            }
+            const size_t cap = (size_t)e->dfl_cap;
+            double *tx = e->dfl_in, *ty = tx + cap, *tm = ty + cap;
+            uint32_t *idx = e->dfl_u32, *tslot = idx + cap;
+            HIPCHK(e, hipMemcpyAsync(idx, fa.idx, sizeof(uint32_t) * (size_t)K,
+                                     hipMemcpyHostToDevice, e->stream));
+            HIPCHK(e, direct_body_targets(n, e->st, idx, K, e->dfl_slot_of, e->ax, e->ay, tx, ty, tm,
+                                          tslot, e->dfl_out + 3 * cap, e->dfl_out + 4 * cap,
+                                          e->stream));
+            HIPCHK(e, hipEventRecord(e->dfl_ev[0], e->stream));
+            direct_targets(e->leaves, e->leaf_count, tx, ty, tm, tslot, K, fp.G, fp.soft2,
+                           e->dfl_out, e->dfl_out + cap, nullptr, e->stream);
+            HIPCHK(e, hipGetLastError());
+            HIPCHK(e, hipEventRecord(e->dfl_ev[1], e->stream));
+            e->dfl_timed = true;
+        }
+        SYNC(e, e->stream);
+        TRY(check_tree_flags(e));
+    }
+    if (fa.run) {
+        std::vector<double> h((size_t)(4 * K));
+        double *host[4] = {h.data(), h.data() + K, h.data() + 2 * K, h.data() + 3 * K};
+        if (run) {
+            const size_t cap = (size_t)e->dfl_cap, bytes = sizeof(double) * (size_t)K;
+            const int plane[4] = {3, 4, 0, 1};  // ax_tree, ay_tree, ax_exact, ay_exact
+            for (int q = 0; q < 4; ++q)
+                HIPCHK(e, hipMemcpy(host[q], e->dfl_out + plane[q] * cap, bytes,
+                                    hipMemcpyDeviceToHost));
+        }
+        double *user[4] = {fa.axt, fa.ayt, fa.axe, fa.aye};
+        for (int q = 0; q < 4; ++q)
+            if (user[q] && K > 0) std::memcpy(user[q], host[q], sizeof(double) * (size_t)K);
+        if (fa.out) force_error_summary(K, host[0], host[1], host[2], host[3], fa.out);
+    }
+    if (e->profiling) TRY(collect_timings(e));
+    return BH_OK;
+}
+
+static int force_error_call(bh_engine *e, const ForceErrorArgs &fa) {
+    ASYNC_GUARD(e);
+    COMM_GUARD(e);
+    return fail_multi_rank(e, force_error_rank(e, fa));
+}
+
+int bh_compute_force_error(bh_engine *e, int64_t n_sample, const int64_t *idx, double *ax_tree,
+                           double *ay_tree, double *ax_exact, double *ay_exact,
+                           bh_force_error *out) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (n_sample < 0 || n_sample > ((int64_t)1 << 28)) {
+        e->err = "bh_compute_force_error: n_sample must be in [0, 2^28]";
+        return BH_E_INVALID;
+    }
+    if (n_sample > 0 && !idx) {
+        e->err = "bh_compute_force_error: idx is NULL";
+        return BH_E_INVALID;
+    }
+    const int64_t n = bh_num_bodies(e);
+    std::vector<uint32_t> idx32((size_t)n_sample);
+    for (int64_t j = 0; j < n_sample; ++j) {
+        if (idx[j] < 0 || idx[j] >= n) {
+            e->err = "bh_compute_force_error: idx[" + std::to_string(j) + "] = " +
+                     std::to_string(idx[j]) + " is outside [0, " + std::to_string(n) + ")";
+            return BH_E_INVALID;
+        }
+        idx32[(size_t)j] = (uint32_t)idx[j];
+    }
+    const ForceErrorArgs all{true, n_sample, idx32.data(), ax_tree, ay_tree, ax_exact, ay_exact,
+                             out};
+    const ForceErrorArgs none{false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    // (every member evaluates as bh_compute_accelerations does; member 0 does the rest)
+    MULTI_ALL(e, force_error_call(m_, r_ == 0 ? all : none));
+    return force_error_call(e, all);
+}
+
+int bh_direct_field_kernel_ms(const bh_engine *e, double *ms) {
+    if (!e || !ms) return BH_E_INVALID;
+    e = MULTI_M0(e);
+    *ms = 0.0;
+    if (!e->dfl_timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, e->dfl_ev[0], e->dfl_ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *ms = (double)f;
+    return BH_OK;
+}
+
+int bh_direct_field_shape(int64_t n_target, int64_t *out3) {
+    if (!out3 || n_target < 0) return BH_E_INVALID;
+    const DirectFieldShape sh = direct_field_shape(n_target);
+    out3[0] = sh.tile;
+    out3[1] = sh.lanes;
+    out3[2] = sh.per_lane;
     return BH_OK;
 }
 

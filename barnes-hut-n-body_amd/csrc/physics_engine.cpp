@@ -240,4 +240,36 @@ void PhysicsEngine::computeField(const std::vector<double> &px, const std::vecto
     pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
 }
 
+void PhysicsEngine::computeFieldDirect(const std::vector<double> &px, const std::vector<double> &py,
+                                       const std::vector<double> &pm, std::vector<double> &ax,
+                                       std::vector<double> &ay, std::vector<double> &phi) {
+    if (px.size() != py.size() || (!pm.empty() && pm.size() != px.size()))
+        throw std::runtime_error("computeFieldDirect: px, py (and pm, unless empty) differ in size");
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    const size_t n = px.size();
+    ax.assign(n, 0.0);
+    ay.assign(n, 0.0);
+    phi.assign(n, 0.0);
+    check(bh_compute_field_direct(eng_, (int64_t)n, px.data(), py.data(),
+                                  pm.empty() ? nullptr : pm.data(), ax.data(), ay.data(),
+                                  phi.data()));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+}
+
+bh_force_error PhysicsEngine::forceError(const std::vector<int64_t> &idx,
+                                         std::vector<double> &axTree, std::vector<double> &ayTree,
+                                         std::vector<double> &axExact,
+                                         std::vector<double> &ayExact) {
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    const size_t k = idx.size();
+    for (std::vector<double> *v : {&axTree, &ayTree, &axExact, &ayExact}) v->assign(k, 0.0);
+    bh_force_error fe{};
+    check(bh_compute_force_error(eng_, (int64_t)k, idx.data(), axTree.data(), ayTree.data(),
+                                 axExact.data(), ayExact.data(), &fe));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+    return fe;
+}
+
 }  // namespace bh

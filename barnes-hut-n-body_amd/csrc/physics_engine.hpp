@@ -87,6 +87,18 @@ public:
     void computeField(const std::vector<double> &px, const std::vector<double> &py,
                       const std::vector<double> &pm, std::vector<double> &ax,
                       std::vector<double> &ay, std::vector<double> &phi);
+    // The same with no cell ever accepted, whatever Config::theta is (bh_compute_field_direct):
+    // the exact field of the list, bit-identical to computeField at theta = 0.
+    void computeFieldDirect(const std::vector<double> &px, const std::vector<double> &py,
+                            const std::vector<double> &pm, std::vector<double> &ax,
+                            std::vector<double> &ay, std::vector<double> &phi);
+    // The tree's force accuracy on the bodies idx[j] of the list (bh_compute_force_error): their
+    // accelerations at Config::theta and their exact ones from one build, each resized to
+    // idx.size(), and the summary of |a_tree - a_exact| / |a_exact|.  State semantics of step()'s
+    // first half -- the jitter is written back into the list.
+    bh_force_error forceError(const std::vector<int64_t> &idx, std::vector<double> &axTree,
+                              std::vector<double> &ayTree, std::vector<double> &axExact,
+                              std::vector<double> &ayExact);
 
     double mergeMaxMass = 4000.0;        // BHA:315
     double mergeMinDist = Config::MIN_R; // BHA:321

@@ -199,7 +199,8 @@ int bh_step(bh_engine *e, int32_t k);
  * caller may only read the mirror it mapped before (bh_map_bodies: the call writes the other
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
- * bh_compute_field, bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_compute_field, bh_compute_field_direct, bh_compute_force_error,
+ * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is.
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
@@ -313,8 +314,9 @@ int bh_potential_kernel_ms(const bh_engine *e, double *ms);
  * gives NaN accelerations and a valid phi, a probe on a centre of mass at soft2 = 0 gives NaN and
  * -inf, a NaN coordinate gives NaN.  Probes outside the root cell, far outside it or non-finite
  * are walked like any other.  With no body in the tree every sum stays +0.0 (phi = -0.0).
- * theta = 0 goes through the same walk, which then opens every node: O(n_probe x nodes); there is
- * no tiled all-pairs kernel for probes.
+ * theta = 0 goes through the same walk, which then opens every node: O(n_probe x nodes); this
+ * call has no tiled all-pairs kernel for probes -- bh_compute_field_direct (below) is that kernel,
+ * at any theta.
  * ax, ay, phi (each nullable) have length n_probe, in the caller's probe order.  n_probe = 0
  * returns BH_OK after the build, launches nothing and leaves bh_field_kernel_ms as it was.
  * BH_E_INVALID (with bh_last_error text): e NULL, n_probe < 0 or > 2^28, px or py NULL with
@@ -325,6 +327,64 @@ int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const doub
 /* HIP-event duration (ms) of the last field kernel launch (bh_compute_field; the probes' keying,
  * sort and upload are outside it); 0 before the first. */
 int bh_field_kernel_ms(const bh_engine *e, double *ms);
+
+/* The exact field of the current state at n_probe points: bh_compute_field with no cell ever
+ * accepted, whatever the engine's theta.  Arguments, probe semantics (a probe is not in the tree;
+ * pm = NULL is mass 1.0; nothing is skipped by identity; nothing special-cases odd inputs),
+ * nullable outputs, n_probe = 0 (BH_OK after the build, nothing launched,
+ * bh_direct_field_kernel_ms left as it was), the 2^28 cap, the BH_E_INVALID cases and the state
+ * semantics (the build with its jitter or the carried tree, tree-flag errors, never sharded; on a
+ * multi-device handle every member builds and member 0 evaluates and answers) are
+ * bh_compute_field's.  Every non-empty leaf that lies under no mass-0 node adds, in pre-order,
+ * the terms written out there: the result is bit-identical to bh_compute_field on an engine that
+ * holds the same state with theta = 0.  It is computed by an LDS-tiled all-pairs kernel over the
+ * tree's leaf sequence (direct_field.hip) instead of that walk: O(n_probe x leaves), the sum of
+ * one probe sequential, the probes in parallel.  With no body in the tree every sum stays +0.0. */
+int bh_compute_field_direct(bh_engine *e, int64_t n_probe, const double *px, const double *py,
+                            const double *pm, double *ax, double *ay, double *phi);
+
+/* The force accuracy of the tree at the engine's theta, on sampled bodies, in one call with one
+ * build.  State semantics are exactly bh_compute_accelerations': buildTree() with its jitter or
+ * the carried tree, then the normal evaluation of every body (sharded on a multi-rank engine; on
+ * a multi-device handle every member evaluates and member 0 does the rest); a tree-flag error is
+ * returned the same way.  idx[j] (j < n_sample) is an index into the current list, the one
+ * bh_get_bodies returns: any order, duplicates allowed.
+ *   ax_tree[j], ay_tree[j]   what bh_compute_accelerations returns for body idx[j] now;
+ *   ax_exact[j], ay_exact[j] what it would return on an engine holding the same state with
+ *     theta = 0: the sum over every non-empty leaf of that same tree but the body's own (skipped
+ *     by identity), in pre-order, by the all-pairs kernel of bh_compute_field_direct.  A body
+ *     outside the root cell has no leaf and is summed like a probe of its own mass; a body of
+ *     mass 0 gets NaN (fx / 0 is not special-cased).
+ * The summary is made on the host, in idx order, in binary64 without contraction:
+ *   rel_j = sqrt(dx*dx + dy*dy) / sqrt(ex*ex + ey*ey),  dx = ax_tree[j] - ax_exact[j], dy alike,
+ *   ex = ax_exact[j], ey = ay_exact[j]; sample j is used iff its four values are finite and the
+ *   denominator is > 0; mean_rel = (sequential sum of rel_j) / n_used; rms_rel = sqrt((sequential
+ *   sum of rel_j * rel_j) / n_used).
+ * The four arrays (length n_sample) and out are each nullable.  n_sample = 0 builds and
+ * evaluates, launches no all-pairs kernel and returns an all-zero out with worst = -1.
+ * BH_E_INVALID (with bh_last_error text) before anything is launched: e NULL, n_sample < 0 or
+ * > 2^28, idx NULL with n_sample > 0, an idx[j] outside [0, N). */
+typedef struct bh_force_error {
+    int64_t n_sample;
+    int64_t n_used;   /* samples whose four accelerations are finite and |a_exact| > 0 */
+    int64_t worst;    /* position in idx[] of max_rel (first on ties); -1 if n_used == 0 */
+    double max_rel, mean_rel, rms_rel;   /* of |a_tree - a_exact| / |a_exact|; 0 if n_used == 0 */
+} bh_force_error;
+int bh_compute_force_error(bh_engine *e, int64_t n_sample, const int64_t *idx,
+                           double *ax_tree, double *ay_tree, double *ax_exact, double *ay_exact,
+                           bh_force_error *out);
+
+/* HIP-event duration (ms) of the last k_direct_targets launch (bh_compute_field_direct or
+ * bh_compute_force_error; uploads, the leaf sequence and the sample gather are outside it); 0
+ * before the first. */
+int bh_direct_field_kernel_ms(const bh_engine *e, double *ms);
+
+/* The launch shape of k_direct_targets for n_target targets: out3 = {leaf records per LDS tile,
+ * lanes per workgroup, targets per lane}.  Host-only: no device, no handle; returned by the
+ * function the launch itself branches on (as bh_launch_plan's values are).  Up to 32 768 targets
+ * {256, 64, 1}: one-wave workgroups, so that a few thousand targets spread over the part; above,
+ * {1024, 256, 2}.  BH_E_INVALID: out3 NULL or n_target < 0. */
+int bh_direct_field_shape(int64_t n_target, int64_t *out3);
 
 /* The body pass of a frame, rasterised on the device: what NBodyPanel.paintComponent's loop over
  * engine.getBodies() paints (PNL:302-307) -- one pixel per body, black if m >= 1000 (PNL:303),
