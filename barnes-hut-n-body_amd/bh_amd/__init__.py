@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = (
     "bh_compute_field", "bh_field_kernel_ms",
     "bh_compute_field_direct", "bh_compute_force_error", "bh_direct_field_kernel_ms",
     "bh_direct_field_shape",
+    "bh_compute_field_grid", "bh_field_grid_of_view", "bh_field_grid_kernel_ms",
+    "bh_field_grid_shape",
 )
 
 
@@ -123,6 +125,33 @@ class BhView(ctypes.Structure):
         ("width", ctypes.c_int32),
         ("height", ctypes.c_int32),
         ("heavy_mass", ctypes.c_double),
+    ]
+
+
+class BhFieldGrid(ctypes.Structure):
+    """struct bh_field_grid (include/bh_engine.h) -- the grid of bh_compute_field_grid: point
+    (c, r) is (x0 + c * dx, y0 + r * dy), one multiply and one add each."""
+    _fields_ = [
+        ("x0", ctypes.c_double),
+        ("y0", ctypes.c_double),
+        ("dx", ctypes.c_double),
+        ("dy", ctypes.c_double),
+        ("nx", ctypes.c_int32),
+        ("ny", ctypes.c_int32),
+    ]
+
+
+class BhFieldGridStats(ctypes.Structure):
+    """struct bh_field_grid_stats (include/bh_engine.h) -- the device-made summary of the three
+    planes of bh_compute_field_grid; indices are row-major, the first on ties, -1 for none."""
+    _fields_ = [
+        ("n_phi", ctypes.c_int64),
+        ("i_phi_min", ctypes.c_int64),
+        ("phi_min", ctypes.c_double),
+        ("phi_max", ctypes.c_double),
+        ("n_acc", ctypes.c_int64),
+        ("i_a2_max", ctypes.c_int64),
+        ("a2_max", ctypes.c_double),
     ]
 
 
@@ -231,6 +260,12 @@ def load_library(path: str | None = None):
                                            ctypes.POINTER(BhForceError)]
     lib.bh_direct_field_kernel_ms.argtypes = [_VP, _D]
     lib.bh_direct_field_shape.argtypes = [ctypes.c_int64, _I64P]
+    lib.bh_compute_field_grid.argtypes = [_VP, ctypes.POINTER(BhFieldGrid), _D, _D, _D,
+                                          ctypes.POINTER(BhFieldGridStats)]
+    lib.bh_field_grid_of_view.argtypes = [ctypes.POINTER(BhView), ctypes.c_int32,
+                                          ctypes.POINTER(BhFieldGrid)]
+    lib.bh_field_grid_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_field_grid_shape.argtypes = [ctypes.c_int32, ctypes.c_int32, _I64P]
     lib.bh_default_view.argtypes = [ctypes.POINTER(BhView)]
     lib.bh_default_view.restype = None
     lib.bh_render_bodies.argtypes = [_VP, ctypes.POINTER(BhView), ctypes.POINTER(ctypes.c_uint8),
@@ -367,6 +402,31 @@ def direct_field_shape(n: int):
     if rc != BH_OK:
         raise BhError(rc, "bh_direct_field_shape: invalid arguments")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def field_grid_shape(nx: int, ny: int):
+    """(tile columns, tile rows, waves per workgroup, tiles) of the kernel behind
+    compute_field_grid for an nx x ny grid (bh_field_grid_shape; host-only, no device)."""
+    out = np.zeros(4, dtype=np.int64)
+    rc = load_library().bh_field_grid_shape(int(nx), int(ny), out.ctypes.data_as(_I64P))
+    if rc != BH_OK:
+        raise BhError(rc, "bh_field_grid_shape: invalid arguments")
+    return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
+
+def field_grid_of_view(view_x=0.0, view_y=0.0, zoom=1.0, width=2400, height=800, cell_px=1,
+                       heavy_mass=1000.0) -> BhFieldGrid:
+    """The grid under a view: one point per cell_px x cell_px block of its pixels, at the block's
+    centre (bh_field_grid_of_view; host-only, no device).  Pass its fields to
+    Engine.compute_field_grid."""
+    lib = load_library()
+    v = BhView(float(view_x), float(view_y), float(zoom), int(width), int(height),
+               float(heavy_mass))
+    g = BhFieldGrid()
+    rc = lib.bh_field_grid_of_view(ctypes.byref(v), int(cell_px), ctypes.byref(g))
+    if rc != BH_OK:
+        raise BhError(rc, lib.bh_last_error(None).decode())
+    return g
 
 
 class NBody3D:
@@ -759,6 +819,33 @@ class Engine:
         force_error (bh_direct_field_kernel_ms)."""
         ms = ctypes.c_double(0.0)
         self._check(self._lib.bh_direct_field_kernel_ms(self._h, ctypes.byref(ms)))
+        return ms.value
+
+    def compute_field_grid(self, x0, y0, dx, dy, nx, ny, want_accel=True, want_phi=True,
+                           want_stats=False):
+        """bh_compute_field_grid: (ax, ay, phi) on the regular grid whose point (c, r) is
+        (x0 + c * dx, y0 + r * dy), as arrays of shape (ny, nx); None for what was not asked
+        (want_accel: ax and ay, want_phi: phi).  Each value is, bit for bit, what compute_field
+        returns for that coordinate with pm = None; the points are made on the device, nothing
+        is uploaded or sorted.  want_stats: a fourth result, the BhFieldGridStats the device
+        reduces from the three planes -- with want_accel = want_phi = False nothing else comes
+        back.  A build, exactly as compute_field."""
+        g = BhFieldGrid(float(x0), float(y0), float(dx), float(dy), int(nx), int(ny))
+        ok = 1 <= g.nx <= 16384 and 1 <= g.ny <= 16384  # (else refused below: no planes)
+        shape = (g.ny, g.nx) if ok else (1, 1)
+        ax = np.empty(shape, dtype=np.float64) if want_accel else None
+        ay = np.empty(shape, dtype=np.float64) if want_accel else None
+        phi = np.empty(shape, dtype=np.float64) if want_phi else None
+        stats = BhFieldGridStats() if want_stats else None
+        self._check(self._lib.bh_compute_field_grid(
+            self._h, ctypes.byref(g), _dp(ax), _dp(ay), _dp(phi),
+            ctypes.byref(stats) if want_stats else None))
+        return (ax, ay, phi, stats) if want_stats else (ax, ay, phi)
+
+    def field_grid_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last grid field kernel launch (bh_field_grid_kernel_ms)."""
+        ms = ctypes.c_double(0.0)
+        self._check(self._lib.bh_field_grid_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
 
     def render_bodies(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,

@@ -670,6 +670,63 @@ hipError_t field_order(int64_t n, const double *px, const double *py, const Geom
                        uint32_t *key, uint32_t *key_s, uint32_t *idx, uint32_t *order,
                        void *scratch, size_t scratch_bytes, hipStream_t s);
 
+// The field on a regular grid (bh_compute_field_grid): no probe arrays, no keys, no sort, no
+// permutation.  One wave is one compact tile of tile_w x tile_h grid points (8 x 8 at 64 lanes;
+// halved alternately, rows first, when bodies_per_wave(nx * ny) gives fewer), the tiles are numbered
+// along the Z-order curve over the tiles_x x tiles_y tile grid (zorder_tile), wpb waves form a
+// workgroup.  Host-only; field_grid_walk launches from it and bh_field_grid_shape reports it.
+struct FieldGridShape {
+    uint32_t tile_w, tile_h;    // grid columns / rows per tile (powers of two, tile_w * tile_h = bpw)
+    uint32_t wpb;               // waves per workgroup
+    uint32_t tiles_x, tiles_y;  // the tile grid
+    uint32_t tiles;             // tiles_x * tiles_y = waves that hold grid points
+};
+FieldGridShape field_grid_shape(int32_t nx, int32_t ny);
+// Tile number w (< tiles_x * tiles_y) on the Z-order curve over the tile grid, x the minor axis:
+// the quadrants of the enclosing power-of-two square in the order (0,0) (1,0) (0,1) (1,1), each
+// clipped to the grid, so that the numbering is compact (no number names a tile outside it).
+__host__ __device__ inline void zorder_tile(uint32_t w, uint32_t tiles_x, uint32_t tiles_y,
+                                            uint32_t &tx, uint32_t &ty) {
+    uint32_t x0 = 0, y0 = 0, cw = tiles_x, ch = tiles_y;  // the clipped region that holds w
+    uint32_t h = 1;
+    while (h < cw || h < ch) h <<= 1;
+    for (h >>= 1; h > 0; h >>= 1) {
+        const uint32_t lw = cw < h ? cw : h, hw = cw - lw;  // columns in the low / high half
+        const uint32_t lh = ch < h ? ch : h, hh = ch - lh;
+        const uint32_t low = lh * cw;  // tiles of the two lower quadrants
+        if (w < low) {
+            ch = lh;
+        } else {
+            w -= low;
+            y0 += h;
+            ch = hh;
+        }
+        const uint32_t left = lw * ch;
+        if (w < left) {
+            cw = lw;
+        } else {
+            w -= left;
+            x0 += h;
+            cw = hw;
+        }
+    }
+    tx = x0;
+    ty = y0;
+}
+// Grid point (c, r) = (g.x0 + (double)c * g.dx, g.y0 + (double)r * g.dy), one multiply and one add
+// each, is a probe of mass 1.0 walked exactly as field_walk walks it; ax, ay, phi (each nullable:
+// not stored) are row-major ny x nx planes.  d_T null: no tree (nodes is not read).
+void field_grid_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T,
+                     const bh_field_grid &g, const Geometry &geo, const ForceParams &fp, double *ax,
+                     double *ay, double *phi, hipStream_t s);
+// bh_field_grid_stats of the three planes (n = nx * ny entries each, none null) into *out, all on
+// the device: workgroup partials over ascending row-major index ranges in `part`
+// (field_grid_stat_partials() structs), then one final workgroup.  Every field is a minimum or
+// maximum under the total order (value, index) or an integer count: no floating-point sum.
+size_t field_grid_stat_partials();
+void field_grid_stats(int64_t n, const double *ax, const double *ay, const double *phi,
+                      bh_field_grid_stats *part, bh_field_grid_stats *out, hipStream_t s);
+
 // ---- launchers (render.hip) ------------------------------------------------------
 // The body pass of a frame (PNL:302-307).  Working planes `packed` and `cnt` (null: no density):
 // render_padded_pixels() uint32 each, zero on entry to render_raster and zero again after

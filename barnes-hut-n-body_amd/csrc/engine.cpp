@@ -246,6 +246,14 @@ struct bh_engine {
     hipEvent_t dfl_ev[2] = {nullptr, nullptr};  // around the last k_direct_targets launch
     bool dfl_timed = false;
 
+    // bh_compute_field_grid (field.hip k_field_grid): result planes of its own, allocated on
+    // first use and kept while nx * ny does not grow; there is nothing to upload
+    double *fgr_out = nullptr;                 // ax, ay, phi planes of fgr_cap grid points
+    bh_field_grid_stats *fgr_stats = nullptr;  // the reduction's partials, then its result
+    int64_t fgr_cap = 0;
+    hipEvent_t fgr_ev[2] = {nullptr, nullptr};  // around the last k_field_grid launch
+    bool fgr_timed = false;
+
     // bh_render_bodies (render.hip): buffers of its own, allocated on first use, kept while the
     // padded pixel count is unchanged.  rnd_packed / rnd_cnt are zero between calls (the resolve
     // kernel re-zeroes what the rasteriser touched); rnd_clean = false: a call failed in between
@@ -1576,7 +1584,48 @@ struct FieldEval {
     // bh_compute_field_direct: every leaf of the tree's leaf sequence summed by the tiled kernel
     // (direct_field.hip) into e->dfl_out, whatever theta is -- no cell is accepted
     bool direct = false;
+    // bh_compute_field_grid: the probes are the points of *grid, formed by the kernel itself
+    // (n_probe, px, py, pm unused) into the planes of e->fgr_out that `planes` names (bit k: ax,
+    // ay, phi), then -- with stats -- their summary into e->fgr_stats
+    const bh_field_grid *grid = nullptr;
+    unsigned planes = 0;
+    bool stats = false;
 };
+
+int field_grid_bufs(bh_engine *e, int64_t points) {
+    if (points > e->fgr_cap || !e->fgr_out) {
+        e->fgr_cap = 0;
+        TRY(dev_alloc(e, e->fgr_out, 3 * (size_t)points));
+        e->fgr_cap = points;
+    }
+    if (!e->fgr_stats) TRY(dev_alloc(e, e->fgr_stats, field_grid_stat_partials()));
+    for (hipEvent_t &ev : e->fgr_ev)
+        if (!ev) HIPCHK(e, hipEventCreate(&ev));
+    return BH_OK;
+}
+
+// k_field_grid between its two events (d_T null: no tree -- no bodies), then the reduction.
+int field_grid_launch(bh_engine *e, const FieldEval &f, const Node *nodes, size_t node_cap,
+                      const uint32_t *d_T, const ForceParams &fp) {
+    const bh_field_grid &g = *f.grid;
+    const int64_t points = (int64_t)g.nx * g.ny;
+    TRY(field_grid_bufs(e, points));
+    const size_t cap = (size_t)e->fgr_cap;
+    double *out[3];
+    for (int k = 0; k < 3; ++k)
+        out[k] = (f.stats || (f.planes >> k & 1u)) ? e->fgr_out + k * cap : nullptr;
+    HIPCHK(e, hipEventRecord(e->fgr_ev[0], e->stream));
+    field_grid_walk(nodes, node_cap, d_T, g, e->geo, fp, out[0], out[1], out[2], e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, hipEventRecord(e->fgr_ev[1], e->stream));
+    e->fgr_timed = true;
+    if (f.stats) {
+        field_grid_stats(points, out[0], out[1], out[2], e->fgr_stats,
+                         e->fgr_stats + field_grid_stat_partials() - 1, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return BH_OK;
+}
 
 int field_bufs(bh_engine *e, int64_t n_probe) {
     if (n_probe > e->fld_cap || !e->fld_in) {
@@ -1722,6 +1771,8 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
     }
     if (fld) {  // the field at the probes on this tree, by this engine alone (theta = 0: the
                 // same walk, which then opens every internal node)
+        if (fld->run && fld->grid)  // the grid's points, formed on the device (k_field_grid)
+            return field_grid_launch(e, *fld, e->nodes, e->node_cap, d_T, fp);
         if (!fld->run || fld->n_probe == 0) return BH_OK;
         if (fld->direct) {  // every leaf, by the tiled kernel (direct_field.hip)
             TRY(ensure_direct(e));
@@ -3197,9 +3248,11 @@ void bh_destroy(bh_engine *e) {
                     e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
                     e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch,
-                    e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of};
+                    e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
+    for (hipEvent_t ev : e->fgr_ev)
+        if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->pot_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->fld_ev)
@@ -3218,7 +3271,14 @@ void bh_destroy(bh_engine *e) {
     delete e;
 }
 
-const char *bh_last_error(const bh_engine *e) { return e ? e->err.c_str() : "null engine"; }
+// what the last call without a handle on this thread refused its arguments for
+// (bh_field_grid_of_view; a static string, null after a success)
+static thread_local const char *handleless_error = nullptr;
+
+const char *bh_last_error(const bh_engine *e) {
+    if (e) return e->err.c_str();
+    return handleless_error ? handleless_error : "null engine";
+}
 
 int bh_set_params(bh_engine *e, const bh_params *p) {
     if (!e || !p) return BH_E_INVALID;
@@ -3855,11 +3915,13 @@ int bh_potential_kernel_ms(const bh_engine *e, double *ms) {
 
 // bh_compute_field on one engine, state semantics of compute_accelerations_rank.  run: this
 // engine evaluates the probes (else it only builds); ax, ay, phi (each nullable): copy-out in the
-// caller's probe order.
-static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi) {
+// caller's probe order.  With fe.grid the probes are the grid's points, the planes row-major, and
+// stats (nullable) receives their summary.
+static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi,
+                      bh_field_grid_stats *stats = nullptr) {
     e->prog_api.store(++e->api_calls);
     HIPCHK(e, hipSetDevice(e->device));
-    const int64_t n = e->n, P = fe.n_probe;
+    const int64_t n = e->n, P = fe.grid ? (int64_t)fe.grid->nx * fe.grid->ny : fe.n_probe;
     const bool run = fe.run && P > 0;
     e->ev_used = 0;
     e->timings_pending = false;
@@ -3871,28 +3933,34 @@ static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay,
         TRY(check_tree_flags(e));
     } else if (run) {  // no bodies, no tree: every sum stays +0.0
         const ForceParams fp = force_params(e);
-        if (fe.direct)
+        if (fe.grid)
+            TRY(field_grid_launch(e, fe, nullptr, 0, nullptr, fp));
+        else if (fe.direct)
             TRY(direct_field_launch(e, fe, false, fp));
         else
             TRY(field_launch(e, fe, nullptr, 0, nullptr, fp));
         SYNC(e, e->stream);
     }
     if (run) {
-        const size_t cap = (size_t)(fe.direct ? e->dfl_cap : e->fld_cap);
+        const size_t cap = (size_t)(fe.grid ? e->fgr_cap : fe.direct ? e->dfl_cap : e->fld_cap);
         const size_t bytes = sizeof(double) * (size_t)P;
-        const double *res = fe.direct ? e->dfl_out : e->fld_out;
+        const double *res = fe.grid ? e->fgr_out : fe.direct ? e->dfl_out : e->fld_out;
         double *out[3] = {ax, ay, phi};
         for (int k = 0; k < 3; ++k)
             if (out[k]) HIPCHK(e, hipMemcpy(out[k], res + k * cap, bytes, hipMemcpyDeviceToHost));
+        if (stats)
+            HIPCHK(e, hipMemcpy(stats, e->fgr_stats + field_grid_stat_partials() - 1,
+                                sizeof(*stats), hipMemcpyDeviceToHost));
     }
     if (e->profiling) TRY(collect_timings(e));
     return BH_OK;
 }
 
-static int field_call(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi) {
+static int field_call(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi,
+                      bh_field_grid_stats *stats = nullptr) {
     ASYNC_GUARD(e);
     COMM_GUARD(e);
-    return fail_multi_rank(e, field_rank(e, fe, ax, ay, phi));
+    return fail_multi_rank(e, field_rank(e, fe, ax, ay, phi, stats));
 }
 
 int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const double *py,
@@ -4104,6 +4172,80 @@ int bh_direct_field_shape(int64_t n_target, int64_t *out3) {
     out3[0] = sh.tile;
     out3[1] = sh.lanes;
     out3[2] = sh.per_lane;
+    return BH_OK;
+}
+
+// null if the grid's shape is usable, else what is wrong with it (the bounds are the view's)
+static const char *field_grid_dims_error(int32_t nx, int32_t ny) {
+    if (nx < 1 || nx > VIEW_MAX_SIDE || ny < 1 || ny > VIEW_MAX_SIDE)
+        return "nx and ny must be in 1..16384";
+    if ((int64_t)nx * (int64_t)ny > VIEW_MAX_PIXELS)
+        return "nx * ny must not exceed 1 << 24";
+    return nullptr;
+}
+
+int bh_compute_field_grid(bh_engine *e, const bh_field_grid *g, double *ax, double *ay,
+                          double *phi, bh_field_grid_stats *stats) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (!g) {
+        e->err = "bh_compute_field_grid: g is NULL";
+        return BH_E_INVALID;
+    }
+    if (const char *why = field_grid_dims_error(g->nx, g->ny)) {
+        e->err = std::string("bh_compute_field_grid: ") + why;
+        return BH_E_INVALID;
+    }
+    if (!std::isfinite(g->x0) || !std::isfinite(g->y0) || !std::isfinite(g->dx) ||
+        !std::isfinite(g->dy)) {
+        e->err = "bh_compute_field_grid: x0, y0, dx and dy must be finite";
+        return BH_E_INVALID;
+    }
+    const bh_field_grid grid = *g;
+    const unsigned planes = (ax ? 1u : 0u) | (ay ? 2u : 0u) | (phi ? 4u : 0u);
+    const FieldEval all{true, 0, nullptr, nullptr, nullptr, false, &grid, planes, stats != nullptr};
+    const FieldEval none{false, 0, nullptr, nullptr, nullptr};
+    // (every member builds, member 0 evaluates and answers: as bh_compute_field)
+    MULTI_ALL(e, r_ == 0 ? field_call(m_, all, ax, ay, phi, stats)
+                         : field_call(m_, none, nullptr, nullptr, nullptr));
+    return field_call(e, all, ax, ay, phi, stats);
+}
+
+int bh_field_grid_kernel_ms(const bh_engine *e, double *ms) {
+    if (!e || !ms) return BH_E_INVALID;
+    e = MULTI_M0(e);
+    *ms = 0.0;
+    if (!e->fgr_timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, e->fgr_ev[0], e->fgr_ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *ms = (double)f;
+    return BH_OK;
+}
+
+int bh_field_grid_shape(int32_t nx, int32_t ny, int64_t *out4) {
+    if (!out4 || field_grid_dims_error(nx, ny)) return BH_E_INVALID;
+    const FieldGridShape sh = field_grid_shape(nx, ny);
+    out4[0] = sh.tile_w;
+    out4[1] = sh.tile_h;
+    out4[2] = sh.wpb;
+    out4[3] = sh.tiles;
+    return BH_OK;
+}
+
+int bh_field_grid_of_view(const bh_view *v, int32_t cell_px, bh_field_grid *g) {
+    const char *why = nullptr;
+    if (!v || !g)
+        why = "bh_field_grid_of_view: v or g is NULL";
+    else if ((why = view_error(*v)) == nullptr && (cell_px < 1 || cell_px > VIEW_MAX_SIDE))
+        why = "bh_field_grid_of_view: cell_px must be in 1..16384";
+    handleless_error = why;
+    if (why) return BH_E_INVALID;
+    const double cell = (double)cell_px;
+    g->nx = (v->width + cell_px - 1) / cell_px;
+    g->ny = (v->height + cell_px - 1) / cell_px;
+    g->dx = g->dy = cell / v->zoom;
+    g->x0 = v->view_x + (0.5 * cell) / v->zoom;
+    g->y0 = v->view_y + (0.5 * cell) / v->zoom;
     return BH_OK;
 }
 

@@ -1,5 +1,7 @@
 // Field query over the flattened quadtree: acceleration and potential at probe points that are
-// not bodies of the system (bh_compute_field, include/bh_engine.h).
+// not bodies of the system (bh_compute_field, include/bh_engine.h), and the same on a regular grid
+// whose points the kernel forms itself (bh_compute_field_grid: k_field_grid and its reductions,
+// after k_field_keys).
 //
 // Probe j is a Body(px, py, 0, 0, pm) that is NOT in the tree.  BHTree.accumulateForce for such a
 // body (BHA:215-239) skips massless nodes (BHA:216), never meets "its own leaf" -- the identity
@@ -196,7 +198,180 @@ __global__ __launch_bounds__(KEY_TB) void k_field_keys(int64_t n, const double *
     idx[i] = (uint32_t)i;
 }
 
+// bh_compute_field_grid: wave v is tile zorder_tile(v) of the grid, lane l its point (l % tile_w,
+// l / tile_w) -- a compact patch of the plane, so the lanes of a wave, the waves of a workgroup
+// and the waves of an XCD run open the same cells.  The coordinates are formed here from the six
+// grid values (one multiply, one add; the build contracts nothing); the guards, the walk and the
+// result arithmetic are k_field's for pm = NULL (G * 1.0 and fx / 1.0 are exact).  Lanes past the
+// right or bottom edge are invalid as k_field's are; each valid lane stores straight to the
+// row-major planes (an 8 x 8 tile: eight 64-byte row segments per plane), a null plane is not
+// stored.
+template <bool OFF32>
+__global__ __launch_bounds__(TB * MAX_WPB) void k_field_grid(const Node *__restrict__ nodes,
+                                                             const uint32_t *__restrict__ d_T,
+                                                             bh_field_grid g, ForceParams fp,
+                                                             double s2root,
+                                                             double *__restrict__ ax,
+                                                             double *__restrict__ ay,
+                                                             double *__restrict__ phi,
+                                                             FieldGridShape sh) {
+    uint32_t b = blockIdx.x;  // runs of FLD_XCD_RUN consecutive waves per XCD (bh_device.hpp)
+    {
+        const uint32_t C = FLD_XCD_RUN / sh.wpb, G = 8 * C, full = gridDim.x / G;
+        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
+    }
+    const uint32_t v = __builtin_amdgcn_readfirstlane(b * sh.wpb + (threadIdx.x >> 6));
+    if (v >= sh.tiles) return;  // (the last workgroup's spare waves)
+    uint32_t tx, ty;
+    zorder_tile(v, sh.tiles_x, sh.tiles_y, tx, ty);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lx = lane & (sh.tile_w - 1u), ly = lane >> __builtin_ctz(sh.tile_w);
+    const uint32_t c = tx * sh.tile_w + lx, r = ty * sh.tile_h + ly;
+    const bool valid = ly < sh.tile_h && c < (uint32_t)g.nx && r < (uint32_t)g.ny;
+    const double bx = valid ? g.x0 + (double)c * g.dx : 0.0;
+    const double by = valid ? g.y0 + (double)r * g.dy : 0.0;
+    const double Gm = fp.G * 1.0;
+    const double soft2 = fp.soft2, theta2 = fp.theta2;
+    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
+    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
+    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
+                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
+    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
+    double fx = 0.0, fy = 0.0, s = 0.0;
+    if (fast)
+        field_walk_wave<true, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
+                                     s);
+    else
+        field_walk_wave<false, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
+                                      s);
+    if (!valid) return;
+    const int64_t j = (int64_t)r * g.nx + c;
+    if (ax) ax[j] = fx / 1.0;  // BHA:390-391
+    if (ay) ay[j] = fy / 1.0;
+    if (phi) phi[j] = -(fp.G * s);
+}
+
+// bh_field_grid_stats: the neutral element and the merge of two summaries of disjoint index sets.
+// Minimum and maximum under (value, index) -- zeros equal by value, the lower index first -- are
+// associative and commutative, so the result does not depend on how the indices were grouped.
+constexpr int GST_TB = 256;
+constexpr int GST_MAX_BLOCKS = 1024;
+
+__device__ __forceinline__ bh_field_grid_stats gstat_none() {
+    return bh_field_grid_stats{0, -1, 0.0, 0.0, 0, -1, 0.0};
+}
+__device__ __forceinline__ void gstat_merge(bh_field_grid_stats &a, const bh_field_grid_stats &b) {
+    if (b.n_phi > 0) {
+        if (a.n_phi == 0 || b.phi_min < a.phi_min ||
+            (b.phi_min == a.phi_min && b.i_phi_min < a.i_phi_min)) {
+            a.phi_min = b.phi_min;
+            a.i_phi_min = b.i_phi_min;
+        }
+        if (a.n_phi == 0 || b.phi_max > a.phi_max) a.phi_max = b.phi_max;
+        a.n_phi += b.n_phi;
+    }
+    if (b.n_acc > 0) {
+        if (a.n_acc == 0 || b.a2_max > a.a2_max ||
+            (b.a2_max == a.a2_max && b.i_a2_max < a.i_a2_max)) {
+            a.a2_max = b.a2_max;
+            a.i_a2_max = b.i_a2_max;
+        }
+        a.n_acc += b.n_acc;
+    }
+}
+__device__ __forceinline__ void gstat_block(bh_field_grid_stats &v, bh_field_grid_stats *lds) {
+    lds[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = GST_TB / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) gstat_merge(lds[threadIdx.x], lds[threadIdx.x + w]);
+        __syncthreads();
+    }
+}
+
+// workgroup b summarises the row-major indices [b chunk, b chunk + chunk)
+__global__ __launch_bounds__(GST_TB) void k_grid_stats_partial(int64_t n, int64_t chunk,
+                                                               const double *__restrict__ ax,
+                                                               const double *__restrict__ ay,
+                                                               const double *__restrict__ phi,
+                                                               bh_field_grid_stats *__restrict__ part) {
+    __shared__ bh_field_grid_stats lds[GST_TB];
+    bh_field_grid_stats v = gstat_none();
+    const int64_t lo = (int64_t)blockIdx.x * chunk;
+    const int64_t hi = lo + chunk < n ? lo + chunk : n;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += GST_TB) {
+        bh_field_grid_stats one = gstat_none();
+        const double p = phi[i], x = ax[i], y = ay[i];
+        if (__builtin_isfinite(p)) {
+            one.n_phi = 1;
+            one.i_phi_min = i;
+            one.phi_min = one.phi_max = p;
+        }
+        if (__builtin_isfinite(x) && __builtin_isfinite(y)) {
+            one.n_acc = 1;
+            one.i_a2_max = i;
+            one.a2_max = x * x + y * y;
+        }
+        gstat_merge(v, one);
+    }
+    gstat_block(v, lds);
+    if (threadIdx.x == 0) part[blockIdx.x] = lds[0];
+}
+
+__global__ __launch_bounds__(GST_TB) void k_grid_stats_final(int blocks,
+                                                             const bh_field_grid_stats *__restrict__ part,
+                                                             bh_field_grid_stats *__restrict__ out) {
+    __shared__ bh_field_grid_stats lds[GST_TB];
+    bh_field_grid_stats v = gstat_none();
+    for (int q = threadIdx.x; q < blocks; q += GST_TB) gstat_merge(v, part[q]);
+    gstat_block(v, lds);
+    if (threadIdx.x == 0) *out = lds[0];
+}
+
 }  // namespace
+
+FieldGridShape field_grid_shape(int32_t nx, int32_t ny) {
+    const uint32_t bpw = bodies_per_wave((int64_t)nx * ny);
+    FieldGridShape sh;
+    sh.tile_w = sh.tile_h = 8;
+    for (uint32_t q = TB; q > bpw; q >>= 1) {  // rows first: 8 x 4, 4 x 4, 4 x 2, ...
+        if (sh.tile_h == sh.tile_w)
+            sh.tile_h >>= 1;
+        else
+            sh.tile_w >>= 1;
+    }
+    sh.tiles_x = ((uint32_t)nx + sh.tile_w - 1) / sh.tile_w;
+    sh.tiles_y = ((uint32_t)ny + sh.tile_h - 1) / sh.tile_h;
+    sh.tiles = sh.tiles_x * sh.tiles_y;
+    sh.wpb = waves_per_group(sh.tiles, bpw);
+    return sh;
+}
+
+void field_grid_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T,
+                     const bh_field_grid &g, const Geometry &geo, const ForceParams &fp, double *ax,
+                     double *ay, double *phi, hipStream_t s) {
+    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
+    const FieldGridShape sh = field_grid_shape(g.nx, g.ny);
+    const unsigned grid = (sh.tiles + sh.wpb - 1) / sh.wpb;
+    if (off32)
+        k_field_grid<true><<<grid, TB * sh.wpb, 0, s>>>(nodes, d_T, g, fp, geo.s2[0], ax, ay, phi,
+                                                        sh);
+    else
+        k_field_grid<false><<<grid, TB * sh.wpb, 0, s>>>(nodes, d_T, g, fp, geo.s2[0], ax, ay, phi,
+                                                         sh);
+}
+
+size_t field_grid_stat_partials() { return (size_t)GST_MAX_BLOCKS + 1; }
+
+void field_grid_stats(int64_t n, const double *ax, const double *ay, const double *phi,
+                      bh_field_grid_stats *part, bh_field_grid_stats *out, hipStream_t s) {
+    // whole workgroup strides per chunk, at most GST_MAX_BLOCKS chunks
+    int64_t chunk = (n + GST_MAX_BLOCKS - 1) / GST_MAX_BLOCKS;
+    chunk = (chunk + GST_TB - 1) / GST_TB * GST_TB;
+    if (chunk < GST_TB) chunk = GST_TB;
+    const int blocks = n > 0 ? (int)((n + chunk - 1) / chunk) : 1;
+    k_grid_stats_partial<<<blocks, GST_TB, 0, s>>>(n, chunk, ax, ay, phi, part);
+    k_grid_stats_final<<<1, GST_TB, 0, s>>>(blocks, part, out);
+}
 
 size_t field_sort_bytes(int64_t n) {
     size_t bytes = 0;

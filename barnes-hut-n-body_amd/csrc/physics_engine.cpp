@@ -257,6 +257,23 @@ void PhysicsEngine::computeFieldDirect(const std::vector<double> &px, const std:
     pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
 }
 
+bh_field_grid_stats PhysicsEngine::computeFieldGrid(const bh_field_grid &grid,
+                                                    std::vector<double> &ax,
+                                                    std::vector<double> &ay,
+                                                    std::vector<double> &phi, bool planes) {
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    // (a grid the engine refuses has no planes: nothing is sized for it)
+    const bool sized = grid.nx > 0 && grid.ny > 0 && (int64_t)grid.nx * grid.ny <= (1 << 24);
+    const size_t n = planes && sized ? (size_t)grid.nx * (size_t)grid.ny : 0;
+    for (std::vector<double> *v : {&ax, &ay, &phi}) v->assign(n, 0.0);
+    bh_field_grid_stats st{};
+    check(bh_compute_field_grid(eng_, &grid, n ? ax.data() : nullptr, n ? ay.data() : nullptr,
+                                n ? phi.data() : nullptr, &st));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+    return st;
+}
+
 bh_force_error PhysicsEngine::forceError(const std::vector<int64_t> &idx,
                                          std::vector<double> &axTree, std::vector<double> &ayTree,
                                          std::vector<double> &axExact,

@@ -92,6 +92,13 @@ public:
     void computeFieldDirect(const std::vector<double> &px, const std::vector<double> &py,
                             const std::vector<double> &pm, std::vector<double> &ax,
                             std::vector<double> &ay, std::vector<double> &phi);
+    // The field on a regular grid made on the device (bh_compute_field_grid; bh_field_grid_of_view
+    // gives the grid under a view): ax, ay, phi are resized to ny * nx, row-major, each value what
+    // computeField returns for that point with pm empty; the device-made summary is returned.
+    // planes = false: the summary alone, the vectors are emptied.  Builds a tree as computeField.
+    bh_field_grid_stats computeFieldGrid(const bh_field_grid &grid, std::vector<double> &ax,
+                                         std::vector<double> &ay, std::vector<double> &phi,
+                                         bool planes = true);
     // The tree's force accuracy on the bodies idx[j] of the list (bh_compute_force_error): their
     // accelerations at Config::theta and their exact ones from one build, each resized to
     // idx.size(), and the summary of |a_tree - a_exact| / |a_exact|.  State semantics of step()'s

@@ -199,7 +199,7 @@ int bh_step(bh_engine *e, int32_t k);
  * caller may only read the mirror it mapped before (bh_map_bodies: the call writes the other
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
- * bh_compute_field, bh_compute_field_direct, bh_compute_force_error,
+ * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
  * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is.
@@ -386,6 +386,59 @@ int bh_direct_field_kernel_ms(const bh_engine *e, double *ms);
  * {1024, 256, 2}.  BH_E_INVALID: out3 NULL or n_target < 0. */
 int bh_direct_field_shape(int64_t n_target, int64_t *out3);
 
+/* The field of the current state on a regular grid, made on the device: the potential map under a
+ * frame.  Nothing is uploaded but the six grid values, no point is keyed or sorted, and the
+ * results land in row-major planes without a permutation.
+ * Grid point (c, r), 0 <= c < nx, 0 <= r < ny, is the probe
+ *     Body(x0 + (double)c * dx, y0 + (double)r * dy, 0, 0, 1.0)
+ * -- each coordinate one multiply and one add in binary64, never fused -- that is not in the tree.
+ * ax, ay, phi (each nullable) are row-major ny x nx planes: index r * nx + c holds, bit for bit,
+ * what bh_compute_field returns for that coordinate with pm = NULL on the same state.  Everything
+ * else is bh_compute_field's, unchanged: every non-empty leaf is taken (a grid point on a body gets
+ * that body's full term), the criterion is strict, the terms are added in pre-order, nothing
+ * special-cases odd inputs, and points outside the root cell -- at 2^40 or at 1e300 -- are walked
+ * like any other.  Zero and negative spacings are legal: the arithmetic decides.  With no body in
+ * the tree every sum stays +0.0 (phi = -0.0).
+ * The tree, the state semantics and the errors are exactly bh_compute_field's: the build with its
+ * jitter or the carried tree, always a full build, never sharded; tree-flag errors returned the
+ * same way; the call leaves what bh_compute_accelerations would leave; on a multi-device handle
+ * every member builds and member 0 evaluates and answers; BH_E_STATE between bh_step_begin and
+ * bh_step_end.
+ * stats (nullable) is computed on the device from the three planes alone, by a fixed-order
+ * reduction without floating-point atomics; extremes are taken under the order (value, row-major
+ * index), zeros comparing equal by value (the sign of a zero extreme is unspecified).  With all
+ * three planes NULL and stats non-NULL the call still evaluates, and nothing comes to the host but
+ * the struct: where the deepest well in view is and what range a colour map should span.
+ * BH_E_INVALID (with bh_last_error text): e or g NULL, nx or ny outside 1..16384,
+ * nx * ny > 1 << 24, a non-finite x0, y0, dx or dy. */
+typedef struct bh_field_grid {
+    double x0, y0;     /* world coordinates of grid point (column 0, row 0) */
+    double dx, dy;     /* spacing along a row / between rows, world units   */
+    int32_t nx, ny;    /* columns, rows: 1..16384 each, nx*ny <= 1<<24      */
+} bh_field_grid;
+typedef struct bh_field_grid_stats {
+    int64_t n_phi;       /* grid points whose phi is finite */
+    int64_t i_phi_min;   /* row-major index of phi_min, first on ties; -1 if n_phi == 0 */
+    double phi_min, phi_max;   /* over those points; 0 if n_phi == 0 */
+    int64_t n_acc;       /* points whose ax and ay are both finite */
+    int64_t i_a2_max;    /* row-major index of a2_max, first on ties; -1 if n_acc == 0 */
+    double a2_max;       /* max of ax*ax + ay*ay (binary64, not contracted); 0 if n_acc == 0 */
+} bh_field_grid_stats;
+int bh_compute_field_grid(bh_engine *e, const bh_field_grid *g, double *ax, double *ay,
+                          double *phi, bh_field_grid_stats *stats);
+
+/* HIP-event duration (ms) of the last k_field_grid launch (bh_compute_field_grid; the stats
+ * reduction and the copy-out are outside it); 0 before the first.  No other call changes it. */
+int bh_field_grid_kernel_ms(const bh_engine *e, double *ms);
+
+/* The launch shape of k_field_grid for an nx x ny grid: out4 = {tile columns, tile rows, waves per
+ * workgroup, tiles}.  One wave is one compact tile of grid points: 8 x 8, halved alternately
+ * (8 x 4, 4 x 4, 4 x 2, ...) while the grid has too few points to fill the part with full waves;
+ * the tiles are numbered along a Z-order curve over the tile grid.  Host-only: no device, no
+ * handle; returned by the function the launch itself branches on (as bh_direct_field_shape's
+ * values are).  BH_E_INVALID: out4 NULL, nx or ny outside 1..16384, nx * ny > 1 << 24. */
+int bh_field_grid_shape(int32_t nx, int32_t ny, int64_t *out4);
+
 /* The body pass of a frame, rasterised on the device: what NBodyPanel.paintComponent's loop over
  * engine.getBodies() paints (PNL:302-307) -- one pixel per body, black if m >= 1000 (PNL:303),
  * white otherwise, a later body of the list overwriting an earlier one -- returned as an image
@@ -428,6 +481,15 @@ int bh_render_bodies(bh_engine *e, const bh_view *v, uint8_t *pixels, uint32_t *
 /* HIP-event duration (ms) of the last bh_render_bodies' two kernels (rasterise + resolve); 0
  * before the first (a call with N = 0 launches nothing and leaves it as it was). */
 int bh_render_kernel_ms(const bh_engine *e, double *ms);
+
+/* The grid of bh_compute_field_grid that lies under a view: one grid point per cell_px x cell_px
+ * block of the view's pixels, at the block's centre.  Host-only.
+ *     nx = ceil(width / cell_px);  ny = ceil(height / cell_px);  dx = dy = cell_px / zoom
+ *     x0 = view_x + (0.5 * cell_px) / zoom;  y0 = view_y + (0.5 * cell_px) / zoom
+ * BH_E_INVALID: v or g NULL, a view bh_render_bodies would refuse (same text), cell_px outside
+ * 1..16384.  The call has no handle: after it returned BH_E_INVALID, bh_last_error(NULL) on the
+ * same thread returns its text (until then, and after a success, "null engine" as ever). */
+int bh_field_grid_of_view(const bh_view *v, int32_t cell_px, bh_field_grid *g);
 
 /* Indices (into the list as it was before the last bh_step call, ascending) of the bodies the
  * merge rule removed during that call — what a shim needs to apply BHA:519's removeAt to the
