@@ -55,6 +55,8 @@ EXPORTED_SYMBOLS = (
     "bh_direct_field_shape",
     "bh_compute_field_grid", "bh_field_grid_of_view", "bh_field_grid_kernel_ms",
     "bh_field_grid_shape",
+    "bh_set_tracers", "bh_num_tracers", "bh_get_tracers", "bh_tracer_kernel_ms",
+    "bh_tracer_launch_shape", "bh_render_tracers",
 )
 
 
@@ -272,6 +274,15 @@ def load_library(path: str | None = None):
                                      ctypes.POINTER(ctypes.c_uint32),
                                      ctypes.POINTER(ctypes.c_uint32)]
     lib.bh_render_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_set_tracers.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D]
+    lib.bh_num_tracers.argtypes = [_VP]
+    lib.bh_num_tracers.restype = ctypes.c_int64
+    lib.bh_get_tracers.argtypes = [_VP, _D, _D, _D, _D, ctypes.c_int64, _I64P]
+    lib.bh_tracer_kernel_ms.argtypes = [_VP, _D, _I64P]
+    lib.bh_tracer_launch_shape.argtypes = [ctypes.c_int64, _I64P]
+    lib.bh_render_tracers.argtypes = [_VP, ctypes.POINTER(BhView),
+                                      ctypes.POINTER(ctypes.c_uint32),
+                                      ctypes.POINTER(ctypes.c_uint32)]
     lib.bh_get_quads.argtypes = [_VP, _D, _D, _D, ctypes.c_int64, _I64P]
     lib.bh_render_quads.argtypes = [_VP, ctypes.POINTER(BhView), ctypes.POINTER(ctypes.c_uint32),
                                     _I64P]
@@ -401,6 +412,16 @@ def direct_field_shape(n: int):
     rc = load_library().bh_direct_field_shape(int(n), out.ctypes.data_as(_I64P))
     if rc != BH_OK:
         raise BhError(rc, "bh_direct_field_shape: invalid arguments")
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def tracer_launch_shape(n: int):
+    """(tracers per wave, waves per workgroup, steps between re-orderings of the lane map) of
+    the tracer walk for `n` tracers (bh_tracer_launch_shape; host-only, no device)."""
+    out = np.zeros(3, dtype=np.int64)
+    rc = load_library().bh_tracer_launch_shape(int(n), out.ctypes.data_as(_I64P))
+    if rc != BH_OK:
+        raise BhError(rc, "bh_tracer_launch_shape: invalid arguments")
     return int(out[0]), int(out[1]), int(out[2])
 
 
@@ -890,6 +911,64 @@ class Engine:
         ms = ctypes.c_double(0.0)
         self._check(self._lib.bh_render_kernel_ms(self._h, ctypes.byref(ms)))
         return ms.value
+
+    def set_tracers(self, x, y, vx=None, vy=None):
+        """bh_set_tracers: replace the engine's tracer list -- massless test particles of mass
+        1.0 that every step() walks over the bodies' own trees and integrates with the same
+        leapfrog, and that exert nothing.  vx, vy None: zeros; empty x, y: no tracers.  One-GPU
+        engines only (BH_E_STATE otherwise, unless the list is empty)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if x.ndim != 1 or y.shape != x.shape:
+            raise ValueError("x and y must be 1-d arrays of equal length")
+        v = []
+        for a in (vx, vy):
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                if a.shape != x.shape:
+                    raise ValueError("vx and vy must have the length of x")
+            v.append(a)
+        self._check(self._lib.bh_set_tracers(self._h, len(x), _dp(x), _dp(y), _dp(v[0]),
+                                             _dp(v[1])))
+
+    def num_tracers(self) -> int:
+        return int(self._lib.bh_num_tracers(self._h))
+
+    def get_tracers(self):
+        """bh_get_tracers: (x, y, vx, vy) of the tracers, in list order."""
+        n = max(self.num_tracers(), 0)
+        out = [np.empty(n, dtype=np.float64) for _ in range(4)]
+        got = ctypes.c_int64(0)
+        self._check(self._lib.bh_get_tracers(self._h, *[_dp(a) for a in out], n,
+                                             ctypes.byref(got)))
+        return tuple(out)
+
+    def tracer_kernel_ms(self):
+        """(average HIP-event ms, launches) of the tracer walks of the last step() call
+        (bh_tracer_kernel_ms); (0.0, 0) unless set_profiling(True)."""
+        ms = ctypes.c_double(0.0)
+        k = ctypes.c_int64(0)
+        self._check(self._lib.bh_tracer_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(k)))
+        return ms.value, k.value
+
+    def render_tracers(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,
+                       owner=True, counts=True):
+        """bh_render_tracers: the tracer pass of a frame with render_bodies' pixel rule.
+        Returns (owner, counts), uint32 of shape (height, width), None for a plane not asked
+        for: the largest tracer index drawn on each pixel (0xFFFFFFFF: none) and the number of
+        tracers drawn on it.  Reads the tracers and changes nothing."""
+        v = BhView(float(view_x), float(view_y), float(zoom),
+                   int(self.params.width_px if width is None else width),
+                   int(self.params.height_px if height is None else height), 1000.0)
+        ok = 1 <= v.width <= 16384 and 1 <= v.height <= 16384  # (else refused below: no planes)
+        shape = (v.height, v.width) if ok else (1, 1)
+        own = np.empty(shape, dtype=np.uint32) if owner else None
+        cnt = np.empty(shape, dtype=np.uint32) if counts else None
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        self._check(self._lib.bh_render_tracers(
+            self._h, ctypes.byref(v), own.ctypes.data_as(u32p) if owner else None,
+            cnt.ctypes.data_as(u32p) if counts else None))
+        return own, cnt
 
     def last_removed(self):
         """Indices (list before the last step() call) removed by the merge rule, ascending."""

@@ -670,6 +670,25 @@ hipError_t field_order(int64_t n, const double *px, const double *py, const Geom
                        uint32_t *key, uint32_t *key_s, uint32_t *idx, uint32_t *order,
                        void *scratch, size_t scratch_bytes, hipStream_t s);
 
+// bh_step's tracers (bh_set_tracers): what tracer_step launches for n tracers -- field_walk's
+// shape -- and the steps between re-orderings of their lane map.  Host-only; tracer_step launches
+// from it and bh_tracer_launch_shape reports it.
+struct TracerShape {
+    uint32_t bpw;      // tracers per wave
+    uint32_t wpb;      // waves per workgroup
+    uint32_t waves;
+    uint32_t reorder;  // R: the engine re-makes `order` (field_order) every R steps
+};
+TracerShape tracer_shape(int64_t n);
+// One evaluation of the n tracers (tx, ty, tvx, tvy by list index, device) on this tree: lane q
+// walks tracer order[q] as field_walk walks a probe of mass 1.0, then applies in registers
+//   KICK_DRIFT: vx += ax * dtHalf; vy += ay * dtHalf; x += vx * dt; y += vy * dt   (BHA:414-422)
+//   KICK_ONLY:  vx += ax * dtHalf; vy += ay * dtHalf                               (BHA:429-432)
+// and writes the tracer back in place.  d_T null: no tree (nodes is not read), every sum +0.0.
+void tracer_step(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *tx, double *ty,
+                 double *tvx, double *tvy, const uint32_t *order, int64_t n, const Geometry &g,
+                 const ForceParams &fp, KickMode kick, double dtHalf, double dt, hipStream_t s);
+
 // The field on a regular grid (bh_compute_field_grid): no probe arrays, no keys, no sort, no
 // permutation.  One wave is one compact tile of tile_w x tile_h grid points (8 x 8 at 64 lanes;
 // halved alternately, rows first, when bodies_per_wave(nx * ny) gives fewer), the tiles are numbered
@@ -732,7 +751,9 @@ void field_grid_stats(int64_t n, const double *ax, const double *ay, const doubl
 // render_padded_pixels() uint32 each, zero on entry to render_raster and zero again after
 // render_resolve.  render_raster: slot i of [0, n), unless a tombstone, drawn at
 // toInt((x - view_x) * zoom), toInt((y - view_y) * zoom) if inside the view, as
-// packed[p] = max(packed[p], ((cidx + 1) << 1) | (m >= heavy_mass)) and cnt[p] += 1.
+// packed[p] = max(packed[p], ((cidx + 1) << 1) | (m >= heavy_mass)) and cnt[p] += 1.  cidx null:
+// slot i is list index i and none is a tombstone; m null: the colour bit stays 0 (the tracer
+// pass, bh_render_tracers).
 // render_resolve: pixels (0 / 1 white / 2 black), owner (caller index or 0xFFFFFFFF) and counts,
 // each nullable (counts iff cnt), each of the padded size and 16-byte aligned.
 size_t render_padded_pixels(int32_t width, int32_t height);

@@ -254,6 +254,19 @@ struct bh_engine {
     hipEvent_t fgr_ev[2] = {nullptr, nullptr};  // around the last k_field_grid launch
     bool fgr_timed = false;
 
+    // bh_set_tracers (field.hip k_tracer_step): the tracer list and its lane map.  Nothing is
+    // allocated while the list is empty; every buffer is sized for exactly trc_n tracers and made
+    // anew when the count changes (a stale lane map would index past the planes)
+    double *trc = nullptr;        // x, y, vx, vy planes of trc_n tracers, list order
+    double *trc_snap = nullptr;   // the same at the start of a bh_step call that may be replayed
+    uint32_t *trc_u32 = nullptr;  // key, sorted key, index, order planes
+    void *trc_scratch = nullptr;
+    size_t trc_scratch_bytes = 0;
+    int64_t trc_n = 0, trc_snap_n = 0;
+    int trc_age = 0, trc_snap_age = 0;  // steps walked with the current lane map
+    double trc_ms_sum = 0.0;            // the tracer walks of the last bh_step call (profiling)
+    int64_t trc_launches = 0;
+
     // bh_render_bodies (render.hip): buffers of its own, allocated on first use, kept while the
     // padded pixel count is unchanged.  rnd_packed / rnd_cnt are zero between calls (the resolve
     // kernel re-zeroes what the rasteriser touched); rnd_clean = false: a call failed in between
@@ -809,10 +822,14 @@ TreeBuffers tree_buffers(bh_engine *e) {
 }
 
 // ---- profiling events ----------------------------------------------------------------
+constexpr int PHASE_START = -2;         // mark(): a start marker even right behind another mark
+constexpr int PHASE_TRACERS = kPhases;  // mark(): the interval was a tracer walk (phase [1])
 int mark(bh_engine *e, int phase) {  // close the interval of `phase` begun at the last mark
     if (!e->profiling) return BH_OK;
     // phases are contiguous on the stream: the previous phase's end mark starts the next one
-    if (phase < 0 && e->ev_used > 0) return BH_OK;
+    // (PHASE_START: a start marker of its own, for an interval that excludes what was queued
+    // since the last mark)
+    if (phase == -1 && e->ev_used > 0) return BH_OK;
     if (e->ev_used + 1 > e->ev.size()) {
         // timing-only events: a device-scope release, no system-scope fence (the default one
         // writes back and invalidates the caches: ~10 us of idle GPU per event in the step)
@@ -838,11 +855,19 @@ int collect_timings(bh_engine *e) {
     e->trav_ms_sum = 0.0;
     e->trav_launches = 0;
     e->trav_samples.clear();
+    e->trc_ms_sum = 0.0;
+    e->trc_launches = 0;
     for (size_t i = 1; i < e->ev_used; ++i) {
         int ph = e->ev_phase[i];
         if (ph < 0) continue;
         float ms = 0.f;
         HIPCHK(e, hipEventElapsedTime(&ms, e->ev[i - 1], e->ev[i]));
+        if (ph == PHASE_TRACERS) {  // a tracer walk: under the traversal's phase, counted apart
+            e->phase_ms[1] += ms;
+            e->trc_ms_sum += ms;
+            ++e->trc_launches;
+            continue;
+        }
         e->phase_ms[ph] += ms;
         if (ph == 1) {  // per evaluation
             e->trav_ms_sum += ms;
@@ -2045,6 +2070,79 @@ int finish_merges(bh_engine *e, uint32_t *overflow, uint32_t *tree_flags = nullp
     return BH_OK;
 }
 
+// ---- tracers (bh_set_tracers) ----------------------------------------------------------
+// The lane map of the tracers: their order along the build's Morton curve (field_order, what
+// bh_compute_field makes for its probes), on the engine's stream.
+int tracer_reorder(bh_engine *e) {
+    const size_t n = (size_t)e->trc_n;
+    uint32_t *key = e->trc_u32, *key_s = key + n, *idx = key_s + n, *order = idx + n;
+    HIPCHK(e, field_order(e->trc_n, e->trc, e->trc + n, e->geo, key, key_s, idx, order,
+                          e->trc_scratch, e->trc_scratch_bytes, e->stream));
+    e->trc_age = 0;
+    return BH_OK;
+}
+
+// One evaluation of the tracers on the tree the bodies' traversal of the same evaluation read
+// (d_T null: no tree), on the engine's stream right behind it.  A step's first walk re-makes a lane
+// map that has served R steps.  No tracers: nothing is launched and no event is recorded.
+int tracer_walk(bh_engine *e, const Node *nodes, size_t node_cap, const uint32_t *d_T,
+                KickMode kick) {
+    const int64_t nt = e->trc_n;
+    if (nt <= 0) return BH_OK;
+    if (kick == KICK_DRIFT) {
+        if (e->trc_age >= (int)tracer_shape(nt).reorder) TRY(tracer_reorder(e));
+        ++e->trc_age;
+    }
+    const size_t s = (size_t)nt;
+    TRY(mark(e, PHASE_START));
+    tracer_step(nodes, node_cap, d_T, e->trc, e->trc + s, e->trc + 2 * s, e->trc + 3 * s,
+                e->trc_u32 + 3 * s, nt, e->geo, force_params(e), kick, e->p.dt * 0.5, e->p.dt,
+                e->stream);
+    HIPCHK(e, hipGetLastError());
+    return mark(e, PHASE_TRACERS);
+}
+
+void tracer_free(bh_engine *e) {
+    for (void **q : {(void **)&e->trc, (void **)&e->trc_snap, (void **)&e->trc_u32,
+                     &e->trc_scratch}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    e->trc_scratch_bytes = 0;
+    e->trc_n = e->trc_snap_n = 0;
+    e->trc_age = 0;
+}
+
+// The tracers at the start of a bh_step call that may be replayed, and back: a replayed call
+// steps them exactly once.  (The lane map a discarded attempt re-made is still a permutation of
+// the same list; its age is the snapshot's, so a replay re-makes it at the same steps.)
+int tracer_snapshot(bh_engine *e) {
+    const int64_t nt = e->trc_n;
+    if (nt <= 0) return BH_OK;
+    if (e->trc_snap_n != nt || !e->trc_snap) {
+        e->trc_snap_n = 0;
+        TRY(dev_alloc(e, e->trc_snap, 4 * (size_t)nt));
+        e->trc_snap_n = nt;
+    }
+    HIPCHK(e, hipMemcpyAsync(e->trc_snap, e->trc, sizeof(double) * 4 * (size_t)nt,
+                             hipMemcpyDeviceToDevice, e->stream));
+    e->trc_snap_age = e->trc_age;
+    return BH_OK;
+}
+
+int tracer_restore(bh_engine *e) {
+    const int64_t nt = e->trc_n;
+    if (nt <= 0) return BH_OK;
+    if (e->trc_snap_n != nt) {
+        e->err = "tracers: a replayed call has no snapshot of the tracer list";
+        return BH_E_STATE;
+    }
+    HIPCHK(e, hipMemcpyAsync(e->trc, e->trc_snap, sizeof(double) * 4 * (size_t)nt,
+                             hipMemcpyDeviceToDevice, e->stream));
+    e->trc_age = e->trc_snap_age;
+    return BH_OK;
+}
+
 // Copy of the state at the start of a bh_step call that may merge: if a step's candidate
 // pairs overflow the mailbox, the call is replayed from here with a larger one, so the rule
 // (BHA:478-520) holds for any number of pairs.
@@ -2068,6 +2166,7 @@ int snapshot(bh_engine *e) {
         e->snap_cap = e->cap;
     }
     e->snap_n = e->n;
+    TRY(tracer_snapshot(e));
     // after a pipelined call the caller's state is the view (the prebuilt tree's jitter is not
     // applied yet): a replay starts from it and builds its own first tree.  The call never writes
     // the view's buffers (its own last step makes a new view from `alt`), so the snapshot takes
@@ -2082,6 +2181,7 @@ int snapshot(bh_engine *e) {
 int restore(bh_engine *e) {
     e->vel_perm = nullptr;  // (the snapshot is complete)
     TRY(copy_state(e, e->snap, e->st, e->snap_n));
+    TRY(tracer_restore(e));
     e->n = e->snap_n;
     TRY(drop_carried_flags(e));
     e->prebuilt = false;
@@ -2466,6 +2566,9 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     HIPCHK(e, hipGetLastError());
     TRY(mark(e, 1));
     TRY(wave_order_next(e, 0, n, s));
+    // the tracers on the tree and node count the traversal just read (the overlapped chain
+    // writes the other node array, the masses and the flags: none of them read here)
+    TRY(tracer_walk(e, e->nodes, e->node_cap, e->T_trav, KICK_ONLY));
     if (last) {
         hipStream_t ps = e->pipe_stream;
         // lastTree's walk (bh_get_quads): this build's sorted keys, prefix lengths and node
@@ -2574,6 +2677,8 @@ int step_once(bh_engine *e, bool last) {
             e->err = "pipelined step: the first evaluation did not fuse its kick";
             return BH_E_STATE;
         }
+        // the tracers on the tree that evaluation walked; the in-place second build follows
+        TRY(tracer_walk(e, e->nodes, e->node_cap, e->base + n, KICK_DRIFT));
         TRY(evaluate_pipelined(e, last));  // a(t+dt), the kick, the merge rule and the next tree
         e->tree_valid = true;
         return BH_OK;
@@ -2593,6 +2698,7 @@ int step_once(bh_engine *e, bool last) {
             }
             TRY(mark(e, 2));
         }
+        TRY(tracer_walk(e, e->nodes, e->node_cap, e->base + n, KICK_DRIFT));
         // the call's last build: a full tree for getTreeForDebug (lastTree, BHA:435) -- or, on a
         // multi-rank engine, a LET build like the others, its input positions kept for a lazy
         // full build in bh_get_quads
@@ -2606,8 +2712,12 @@ int step_once(bh_engine *e, bool last) {
             HIPCHK(e, hipGetLastError());
             TRY(mark(e, 2));
         }
+        TRY(tracer_walk(e, e->nodes, e->node_cap, e->base + n, KICK_ONLY));
         e->tree_valid = !let2;  // lastTree = root (BHA:435)
         e->lazy_tree = lazy && let2;
+    } else {  // no bodies, no tree: every sum is +0.0 and the tracers drift on straight lines
+        TRY(tracer_walk(e, nullptr, 0, nullptr, KICK_DRIFT));
+        TRY(tracer_walk(e, nullptr, 0, nullptr, KICK_ONLY));
     }
     if (last)  // the call's removal count before its last merge rule (finish_merges, BHA:526)
         HIPCHK(e, hipMemcpyAsync(e->scalars + 8, e->scalars + 2, sizeof(uint32_t),
@@ -3248,7 +3358,8 @@ void bh_destroy(bh_engine *e) {
                     e->lr_slot, e->lr_scratch, e->phi, e->diag_part, e->rnd_packed, e->rnd_cnt,
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
                     e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch,
-                    e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats};
+                    e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats,
+                    e->trc, e->trc_snap, e->trc_u32, e->trc_scratch};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (hipEvent_t ev : e->fgr_ev)
@@ -3432,6 +3543,8 @@ static int step_call(bh_engine *e, int32_t k) {
 static int step_call_rank(bh_engine *e, int32_t k) {
     e->prog_api.store(++e->api_calls);
     HIPCHK(e, hipSetDevice(e->device));
+    e->trc_ms_sum = 0.0;  // bh_tracer_kernel_ms: this call's walks, timed only while profiling
+    e->trc_launches = 0;
     const bool may_merge = k > 0 && e->n > 1 && e->p.merge_min_dist > 0.0 && e->heavy_possible;
     // a multi-rank call with LET builds may have to be replayed with a larger subset capacity
     const bool may_let = k > 0 && e->n > 0 && (e->comm || e->group || e->solo) && let_active(e) &&
@@ -4372,6 +4485,128 @@ int bh_render_kernel_ms(const bh_engine *e, double *ms) {
     float f = 0.f;
     if (hipEventElapsedTime(&f, e->rnd_ev[0], e->rnd_ev[1]) != hipSuccess) return BH_E_DEVICE;
     *ms = (double)f;
+    return BH_OK;
+}
+
+int bh_set_tracers(bh_engine *e, int64_t n, const double *x, const double *y, const double *vx,
+                   const double *vy) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (n < 0 || n > ((int64_t)1 << 28)) {
+        e->err = "bh_set_tracers: n must be in [0, 2^28]";
+        return BH_E_INVALID;
+    }
+    if (n > 0 && (!x || !y)) {
+        e->err = "bh_set_tracers: x or y is NULL";
+        return BH_E_INVALID;
+    }
+    if (e->multi || e->comm || e->group || e->solo) {
+        if (n == 0) return BH_OK;  // (such an engine never holds tracers)
+        e->err = "bh_set_tracers: tracers need the one-GPU engine (bh_create): this engine's steps "
+                 "shard their builds as locally essential trees, which a tracer cannot walk";
+        return BH_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    SYNC(e, e->stream);
+    if (n != e->trc_n) {  // another count: every buffer anew, the lane map with them
+        tracer_free(e);
+        if (n == 0) return BH_OK;
+        const size_t cap = (size_t)n;
+        TRY(dev_alloc(e, e->trc, 4 * cap));
+        TRY(dev_alloc(e, e->trc_u32, 4 * cap));
+        e->trc_scratch_bytes = field_sort_bytes(n);
+        HIPCHK(e, hipMalloc(&e->trc_scratch, e->trc_scratch_bytes ? e->trc_scratch_bytes : 1));
+        e->trc_n = n;
+    }
+    if (n == 0) return BH_OK;
+    const size_t s = (size_t)n, bytes = sizeof(double) * s;
+    const double *src[4] = {x, y, vx, vy};
+    for (int k = 0; k < 4; ++k) {
+        if (src[k])
+            HIPCHK(e, hipMemcpyAsync(e->trc + k * s, src[k], bytes, hipMemcpyHostToDevice,
+                                     e->stream));
+        else  // (all-zero bytes: +0.0)
+            HIPCHK(e, hipMemsetAsync(e->trc + k * s, 0, bytes, e->stream));
+    }
+    TRY(tracer_reorder(e));
+    SYNC(e, e->stream);
+    return BH_OK;
+}
+
+int64_t bh_num_tracers(const bh_engine *e) {
+    if (!e) return -1;
+    return e->trc_n;  // (a multi-device handle holds none)
+}
+
+int bh_get_tracers(bh_engine *e, double *x, double *y, double *vx, double *vy, int64_t cap,
+                   int64_t *n_out) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    const int64_t n = e->trc_n;
+    if (n_out) *n_out = n;
+    if (cap < n) return BH_E_CAPACITY;
+    if (n == 0) return BH_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    double *dst[4] = {x, y, vx, vy};
+    for (int k = 0; k < 4; ++k)
+        if (dst[k])
+            HIPCHK(e, hipMemcpyAsync(dst[k], e->trc + k * (size_t)n, sizeof(double) * (size_t)n,
+                                     hipMemcpyDeviceToHost, e->stream));
+    SYNC(e, e->stream);
+    return BH_OK;
+}
+
+int bh_tracer_kernel_ms(const bh_engine *e, double *avg_ms, int64_t *launches) {
+    if (!e || !avg_ms) return BH_E_INVALID;
+    if (e->async_running && std::this_thread::get_id() != e->step_thr.get_id()) return BH_E_STATE;
+    *avg_ms = e->trc_launches ? e->trc_ms_sum / (double)e->trc_launches : 0.0;
+    if (launches) *launches = e->trc_launches;
+    return BH_OK;
+}
+
+int bh_tracer_launch_shape(int64_t n_tracer, int64_t *out3) {
+    if (!out3 || n_tracer < 0 || n_tracer > ((int64_t)1 << 28)) return BH_E_INVALID;
+    const TracerShape sh = tracer_shape(n_tracer);
+    out3[0] = sh.bpw;
+    out3[1] = sh.wpb;
+    out3[2] = sh.reorder;
+    return BH_OK;
+}
+
+int bh_render_tracers(bh_engine *e, const bh_view *v, uint32_t *owner, uint32_t *counts) {
+    if (!e || !v) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (const char *why = view_error(*v)) {
+        e->err = why;
+        return BH_E_INVALID;
+    }
+    const size_t npix = (size_t)v->width * (size_t)v->height;
+    const int64_t n = e->trc_n;
+    if (n <= 0) {  // nothing drawn: no device work
+        if (owner) std::memset(owner, 0xFF, sizeof(uint32_t) * npix);
+        if (counts) std::memset(counts, 0, sizeof(uint32_t) * npix);
+        return BH_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    // bh_render_bodies' working planes and kernels; the list's own order stands for cidx and
+    // there is no mass plane (no colour); its kernel timing is left as it was
+    const size_t pad = render_padded_pixels(v->width, v->height);
+    TRY(render_buffers(e, pad, false, owner != nullptr, counts != nullptr));
+    e->rnd_clean = false;
+    render_raster(n, e->trc, e->trc + (size_t)n, nullptr, nullptr, *v, e->rnd_packed,
+                  counts ? e->rnd_cnt : nullptr, e->stream);
+    HIPCHK(e, hipGetLastError());
+    render_resolve(pad, e->rnd_packed, counts ? e->rnd_cnt : nullptr, nullptr,
+                   owner ? e->rnd_owner : nullptr, counts ? e->rnd_counts : nullptr, e->stream);
+    HIPCHK(e, hipGetLastError());
+    e->rnd_clean = true;
+    if (owner)
+        HIPCHK(e, hipMemcpyAsync(owner, e->rnd_owner, sizeof(uint32_t) * npix,
+                                 hipMemcpyDeviceToHost, e->stream));
+    if (counts)
+        HIPCHK(e, hipMemcpyAsync(counts, e->rnd_counts, sizeof(uint32_t) * npix,
+                                 hipMemcpyDeviceToHost, e->stream));
+    SYNC(e, e->stream);
     return BH_OK;
 }
 

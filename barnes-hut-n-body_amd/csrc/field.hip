@@ -1,7 +1,8 @@
 // Field query over the flattened quadtree: acceleration and potential at probe points that are
 // not bodies of the system (bh_compute_field, include/bh_engine.h), and the same on a regular grid
 // whose points the kernel forms itself (bh_compute_field_grid: k_field_grid and its reductions,
-// after k_field_keys).
+// after k_field_keys), and the same walk carried through time for bh_step's tracers
+// (k_tracer_step: the leapfrog's kick and drift as the walk's epilogue).
 //
 // Probe j is a Body(px, py, 0, 0, pm) that is NOT in the tree.  BHTree.accumulateForce for such a
 // body (BHA:215-239) skips massless nodes (BHA:216), never meets "its own leaf" -- the identity
@@ -184,6 +185,64 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_field(const Node *__restrict__
     ax[j] = fx / bm;  // BHA:390-391
     ay[j] = fy / bm;
     phi[j] = -(fp.G * s);
+}
+
+// bh_step's tracers (bh_set_tracers): tracer t is a probe of mass 1.0 that is carried through
+// time.  Guards, walk and result arithmetic are k_field's for pm = NULL (G * 1.0 and fx / 1.0 are
+// exact); instead of storing a and phi the lane applies the leapfrog's lines to its own tracer in
+// registers -- KICK_DRIFT = BHA:414-422, KICK_ONLY = BHA:429-432, the operations of k_kick_drift /
+// k_kick in their order, never fused -- and writes the tracer's values back in place, by list
+// index.  The potential's sum is not used here, so its multiply and add are dropped with it.
+template <int KICK, bool OFF32>
+__global__ __launch_bounds__(TB * MAX_WPB) void k_tracer_step(const Node *__restrict__ nodes,
+                                                              const uint32_t *__restrict__ d_T,
+                                                              double *__restrict__ tx,
+                                                              double *__restrict__ ty,
+                                                              double *__restrict__ tvx,
+                                                              double *__restrict__ tvy,
+                                                              const uint32_t *__restrict__ order,
+                                                              int64_t n, ForceParams fp,
+                                                              double s2root, double dtHalf,
+                                                              double dt, uint32_t bpw,
+                                                              uint32_t wpb) {
+    static_assert(KICK == KICK_DRIFT || KICK == KICK_ONLY, "a tracer walk always kicks");
+    uint32_t b = blockIdx.x;  // runs of FLD_XCD_RUN consecutive waves per XCD (bh_device.hpp)
+    {
+        const uint32_t C = FLD_XCD_RUN / wpb, G = 8 * C, full = gridDim.x / G;
+        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
+    }
+    const uint32_t v = b * wpb + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t q = (int64_t)v * bpw + lane;
+    const bool valid = lane < bpw && q < n;
+    const int64_t j = valid ? (int64_t)order[q] : 0;  // the tracer's list index
+    const double bx = valid ? tx[j] : 0.0;
+    const double by = valid ? ty[j] : 0.0;
+    const double Gm = fp.G * 1.0;  // (Config.G * b.m) is evaluated first (BHA:256)
+    const double soft2 = fp.soft2, theta2 = fp.theta2;
+    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
+    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
+    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
+                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
+    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
+    double fx = 0.0, fy = 0.0, s = 0.0;
+    if (fast)
+        field_walk_wave<true, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
+                                     s);
+    else
+        field_walk_wave<false, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
+                                      s);
+    if (!valid) return;
+    const double ax = fx / 1.0;  // BHA:390-391
+    const double ay = fy / 1.0;
+    const double vx = tvx[j] + ax * dtHalf;  // BHA:414-415 / BHA:429-430
+    const double vy = tvy[j] + ay * dtHalf;
+    tvx[j] = vx;
+    tvy[j] = vy;
+    if (KICK == KICK_DRIFT) {  // BHA:416-417
+        tx[j] = bx + vx * dt;
+        ty[j] = by + vy * dt;
+    }
 }
 
 // The build's own key of a probe's position (total: a NaN or out-of-root probe takes the
@@ -408,6 +467,49 @@ void field_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const d
     else
         k_field<false><<<grid, TB * wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0],
                                                  ax, ay, phi, bpw, wpb);
+}
+
+#ifndef BH_TRACER_REORDER
+// steps between re-orderings of the tracers' lane map.  C3 with 10^6 tracers on the bodies' start
+// positions, ms per step over 128-step calls, two alternating rounds (DESIGN.md §15,
+// profiles/tracers_timing.jsonl): R = 1 4.08 / 4.08, 4 4.44 / 4.44, 16 5.43 / 5.47, 64 6.60 /
+// 6.69 against 1.48 without tracers -- the keys and the radix sort of 10^6 tracers cost less
+// than one step's loss of lane coherence
+#define BH_TRACER_REORDER 1
+#endif
+static_assert(BH_TRACER_REORDER >= 1, "the lane map is re-made every R >= 1 steps");
+
+TracerShape tracer_shape(int64_t n) {
+    TracerShape sh;
+    sh.bpw = bodies_per_wave(n);
+    sh.waves = (uint32_t)((n + sh.bpw - 1) / sh.bpw);
+    sh.wpb = waves_per_group(sh.waves, sh.bpw);
+    sh.reorder = BH_TRACER_REORDER;
+    return sh;
+}
+
+void tracer_step(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *tx, double *ty,
+                 double *tvx, double *tvy, const uint32_t *order, int64_t n, const Geometry &g,
+                 const ForceParams &fp, KickMode kick, double dtHalf, double dt, hipStream_t s) {
+    if (n <= 0) return;
+    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
+    const TracerShape sh = tracer_shape(n);
+    const unsigned grid = (sh.waves + sh.wpb - 1) / sh.wpb, tb = TB * sh.wpb;
+#define BH_TRACER_LAUNCH(K, O)                                                                    \
+    k_tracer_step<K, O><<<grid, tb, 0, s>>>(nodes, d_T, tx, ty, tvx, tvy, order, n, fp, g.s2[0], \
+                                            dtHalf, dt, sh.bpw, sh.wpb)
+    if (kick == KICK_DRIFT) {
+        if (off32)
+            BH_TRACER_LAUNCH(KICK_DRIFT, true);
+        else
+            BH_TRACER_LAUNCH(KICK_DRIFT, false);
+    } else {
+        if (off32)
+            BH_TRACER_LAUNCH(KICK_ONLY, true);
+        else
+            BH_TRACER_LAUNCH(KICK_ONLY, false);
+    }
+#undef BH_TRACER_LAUNCH
 }
 
 }  // namespace bh

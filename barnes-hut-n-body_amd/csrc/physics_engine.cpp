@@ -289,4 +289,34 @@ bh_force_error PhysicsEngine::forceError(const std::vector<int64_t> &idx,
     return fe;
 }
 
+void PhysicsEngine::setTracers(const std::vector<double> &x, const std::vector<double> &y,
+                               const std::vector<double> &vx, const std::vector<double> &vy) {
+    const size_t n = x.size();
+    if (y.size() != n || (!vx.empty() && vx.size() != n) || (!vy.empty() && vy.size() != n))
+        throw std::runtime_error("setTracers: x, y (and vx, vy, unless empty) differ in size");
+    check(bh_set_tracers(eng_, (int64_t)n, x.data(), y.data(), vx.empty() ? nullptr : vx.data(),
+                         vy.empty() ? nullptr : vy.data()));
+}
+
+int64_t PhysicsEngine::numTracers() const { return bh_num_tracers(eng_); }
+
+void PhysicsEngine::getTracers(std::vector<double> &x, std::vector<double> &y,
+                               std::vector<double> &vx, std::vector<double> &vy) {
+    const size_t n = (size_t)bh_num_tracers(eng_);
+    for (std::vector<double> *v : {&x, &y, &vx, &vy}) v->assign(n, 0.0);
+    int64_t got = 0;
+    check(bh_get_tracers(eng_, x.data(), y.data(), vx.data(), vy.data(), (int64_t)n, &got));
+}
+
+void PhysicsEngine::renderTracers(const bh_view &view, std::vector<uint32_t> &owner,
+                                  std::vector<uint32_t> &counts) {
+    // (a view the engine refuses has no planes: nothing is sized for it)
+    const bool sized = view.width > 0 && view.height > 0 &&
+                       (int64_t)view.width * view.height <= (1 << 24);
+    const size_t n = sized ? (size_t)view.width * (size_t)view.height : 0;
+    owner.assign(n, 0xFFFFFFFFu);
+    counts.assign(n, 0u);
+    check(bh_render_tracers(eng_, &view, n ? owner.data() : nullptr, n ? counts.data() : nullptr));
+}
+
 }  // namespace bh

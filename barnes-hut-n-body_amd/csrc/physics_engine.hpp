@@ -107,6 +107,18 @@ public:
                               std::vector<double> &ayTree, std::vector<double> &axExact,
                               std::vector<double> &ayExact);
 
+    // Tracers (bh_set_tracers; no reference counterpart): massless test particles of mass 1.0 that
+    // every step() carries along on the bodies' own trees and that exert nothing.  A list of the
+    // engine's own, kept across resetBodies; vx, vy empty: zeros; empty x, y: no tracers.
+    void setTracers(const std::vector<double> &x, const std::vector<double> &y,
+                    const std::vector<double> &vx, const std::vector<double> &vy);
+    int64_t numTracers() const;
+    void getTracers(std::vector<double> &x, std::vector<double> &y, std::vector<double> &vx,
+                    std::vector<double> &vy);
+    // Their pass of a frame (bh_render_tracers): owner and counts resized to height x width.
+    void renderTracers(const bh_view &view, std::vector<uint32_t> &owner,
+                       std::vector<uint32_t> &counts);
+
     double mergeMaxMass = 4000.0;        // BHA:315
     double mergeMinDist = Config::MIN_R; // BHA:321
 

@@ -38,7 +38,7 @@ __global__ __launch_bounds__(TB) void k_raster(int64_t n, const double *__restri
     const int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x;
     uint32_t pix = NO_PIXEL, val = 0u;
     if (i < n) {
-        const uint32_t c = cidx[i];
+        const uint32_t c = cidx ? cidx[i] : (uint32_t)i;  // (no cidx: the list's own order)
         if (!(c & CIDX_DEAD)) {
             const double tx = (x[i] - v.view_x) * v.zoom;
             const double ty = (y[i] - v.view_y) * v.zoom;
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(TB) void k_raster(int64_t n, const double *__restri
                 const int32_t sx = nx ? 0 : (int32_t)tx;  // in (-1, width): the cast is defined
                 const int32_t sy = ny ? 0 : (int32_t)ty;
                 pix = (uint32_t)sy * (uint32_t)v.width + (uint32_t)sx;
-                val = ((c + 1u) << 1) | (m[i] >= v.heavy_mass ? 1u : 0u);
+                val = ((c + 1u) << 1) | (m && m[i] >= v.heavy_mass ? 1u : 0u);
             }
         }
     }

@@ -202,7 +202,7 @@ int bh_step(bh_engine *e, int32_t k);
  * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
  * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
- * way, as bh_get_quads is.
+ * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers.
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
  * once its last merge rule is done, before its last traversal; else when the call ends -- and
  * returns the mirror planes x, y, m of the list after the call (n_out bodies; the other buffer
@@ -490,6 +490,73 @@ int bh_render_kernel_ms(const bh_engine *e, double *ms);
  * 1..16384.  The call has no handle: after it returned BH_E_INVALID, bh_last_error(NULL) on the
  * same thread returns its text (until then, and after a success, "null engine" as ever). */
 int bh_field_grid_of_view(const bh_view *v, int32_t cell_px, bh_field_grid *g);
+
+/* Tracers: massless test particles stepped with the bodies -- points that feel the system, exert
+ * nothing on it and are integrated by the same leapfrog, on the same trees, in the same bh_step
+ * call (the restricted N-body experiment: two massive disks plus 10^6 tracers that draw the tails).
+ * The engine holds a second list of n_tracer tracers (x, y, vx, vy) in binary64, in the caller's
+ * order, independent of the body list.  Tracer t is a Body(x, y, vx, vy, 1.0) that is never
+ * inserted into any tree -- the reference's body outside the root cell, "not inserted but walked
+ * and integrated" (BHA:126), anywhere in the plane.  In every PhysicsEngine.step() that bh_step
+ * runs, with `root` the tree the bodies use for that evaluation (after its jitter):
+ *     (fx, fy) = root.accumulateForce(t)  -- exactly bh_compute_field's terms for pm = NULL:
+ *                massless nodes skipped, EVERY non-empty leaf taken, an internal node taken iff
+ *                s2 < theta^2 * dist2 (strict), terms added in pre-order from +0.0,
+ *                f = (G * 1.0) * m * invR2;  ax = fx / 1.0;  ay = fy / 1.0
+ *     first evaluation:   vx += ax * dtHalf;  vy += ay * dtHalf;  x += vx * dt;  y += vy * dt
+ *     second evaluation:  vx += ax * dtHalf;  vy += ay * dtHalf        (BHA:412-432, never fused)
+ * Tracers never take part in the merge rule: never victims, never heavy, not counted in N.
+ * Nothing special-cases odd inputs: NaN and 1e300 coordinates give what the arithmetic gives; with
+ * no body in the tree every sum is +0.0, the tracers drift on straight lines, and -0.0 + 0.0 turns
+ * a -0.0 velocity into +0.0.  At theta = 0 the bodies use the all-pairs kernel and the tracers the
+ * same walk, which then opens every node (bit-identical, as bh_compute_field documents; there is
+ * no tiled tracer kernel).  A tracer's result does not depend on n_tracer, on its position in the
+ * list, on the internal lane order or on how steps are grouped into calls (k steps in one call =
+ * k one-step calls), and the bodies' results are bit for bit what they are without tracers.
+ *
+ * bh_set_tracers replaces the whole list (vx, vy nullable: zeros; n = 0 clears it and frees its
+ * buffers).  BH_E_INVALID: e NULL, n < 0 or n > 2^28, x or y NULL with n > 0.  BH_E_STATE with
+ * n > 0 on any engine that is not the one-GPU engine -- bh_create_dist, bh_create_local and
+ * bh_create_solo engines and a multi-device handle with more than one member: their steps shard
+ * their builds as locally essential trees, which a tracer cannot walk (bh_last_error says so);
+ * n = 0 is accepted everywhere.
+ * The list persists across bh_reset_bodies, bh_set_params and bh_load_state; it is not written by
+ * bh_save_state (the BHSTATE1 format is unchanged) and not touched by any bh_compute_*,
+ * bh_get_quads or bh_render_* call: only bh_step, bh_step_begin / bh_step_end and bh_set_tracers
+ * change it.  bh_step(e, 0) leaves it alone.  After bh_step_end the tracers are final;
+ * bh_step_positions says nothing about them.  A call replayed for a merge mailbox overflow steps
+ * them exactly once.
+ * bh_get_tracers: copy-out in list order, any plane nullable; BH_E_CAPACITY with *n_out =
+ * n_tracer if cap < n_tracer.  bh_num_tracers: -1 for a NULL handle. */
+int bh_set_tracers(bh_engine *e, int64_t n, const double *x, const double *y, const double *vx,
+                   const double *vy);
+int64_t bh_num_tracers(const bh_engine *e);
+int bh_get_tracers(bh_engine *e, double *x, double *y, double *vx, double *vy, int64_t cap,
+                   int64_t *n_out);
+
+/* Average HIP-event duration (ms) of the tracer walks of the last bh_step call and their number
+ * (two per step), as bh_traverse_kernel_ms reports the traversals.  Taken only while
+ * bh_set_profiling(e, 1) -- otherwise *launches = 0 and no event is recorded; the walks are then
+ * also counted under phase [1] of bh_last_timings. */
+int bh_tracer_kernel_ms(const bh_engine *e, double *avg_ms, int64_t *launches);
+
+/* The launch shape of the tracer walk for n_tracer tracers: out3 = {tracers per wave, waves per
+ * workgroup, R}.  The first two are bh_compute_field's for as many probes; R is the number of
+ * steps between re-orderings of the lane map (lane q walks tracer order[q]; the map is the
+ * tracers' order along the build's Morton curve, made by bh_set_tracers and re-made every R steps
+ * before the step's first walk -- results do not depend on it).  Host-only: no device, no handle;
+ * returned by the function the launch itself branches on (as bh_direct_field_shape's values are).
+ * BH_E_INVALID: out3 NULL, n_tracer < 0 or > 2^28. */
+int bh_tracer_launch_shape(int64_t n_tracer, int64_t *out3);
+
+/* The tracer pass of a frame: bh_render_bodies' pixel rule over the tracer list (the toInt rule;
+ * drawn iff t is NaN or -1 < t < size; the later list index wins).  owner[p] is the largest tracer
+ * index drawn on p, 0xFFFFFFFF where nothing was drawn; counts[p] the number of tracers drawn on
+ * p; either may be NULL.  The view is checked as by bh_render_bodies (same BH_E_INVALID cases and
+ * bh_last_error text; heavy_mass is checked but not used); state semantics are bh_render_bodies':
+ * no build, no state change, BH_E_STATE between bh_step_begin and bh_step_end.  n_tracer = 0:
+ * owner all 0xFFFFFFFF, counts all 0. */
+int bh_render_tracers(bh_engine *e, const bh_view *v, uint32_t *owner, uint32_t *counts);
 
 /* Indices (into the list as it was before the last bh_step call, ascending) of the bodies the
  * merge rule removed during that call — what a shim needs to apply BHA:519's removeAt to the
