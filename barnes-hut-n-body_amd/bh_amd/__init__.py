@@ -604,6 +604,12 @@ class Engine:
         if rc != BH_OK:
             raise BhError(rc, self._lib.bh_last_error(self._h).decode())
 
+    def _kernel_ms(self, fn) -> float:
+        """One of the bh_*_kernel_ms calls that return a single value."""
+        ms = ctypes.c_double(0.0)
+        self._check(fn(self._h, ctypes.byref(ms)))
+        return ms.value
+
     def close(self):
         if self._h and self._owned:
             self._lib.bh_destroy(self._h)
@@ -760,9 +766,7 @@ class Engine:
 
     def potential_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last potential kernel launch (bh_potential_kernel_ms)."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._lib.bh_potential_kernel_ms(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self._lib.bh_potential_kernel_ms)
 
     def compute_field(self, px, py, pm=None, want_accel=True, want_phi=True):
         """bh_compute_field: (ax, ay, phi) at the probe points (px, py), in probe order; None
@@ -789,9 +793,7 @@ class Engine:
 
     def field_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last field kernel launch (bh_field_kernel_ms)."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._lib.bh_field_kernel_ms(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self._lib.bh_field_kernel_ms)
 
     def compute_field_direct(self, px, py, pm=None, want_accel=True, want_phi=True):
         """bh_compute_field_direct: compute_field with no cell ever accepted, whatever the
@@ -838,9 +840,7 @@ class Engine:
     def direct_field_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last all-pairs kernel launch of compute_field_direct or
         force_error (bh_direct_field_kernel_ms)."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._lib.bh_direct_field_kernel_ms(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self._lib.bh_direct_field_kernel_ms)
 
     def compute_field_grid(self, x0, y0, dx, dy, nx, ny, want_accel=True, want_phi=True,
                            want_stats=False):
@@ -865,9 +865,7 @@ class Engine:
 
     def field_grid_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last grid field kernel launch (bh_field_grid_kernel_ms)."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._lib.bh_field_grid_kernel_ms(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self._lib.bh_field_grid_kernel_ms)
 
     def render_bodies(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,
                       heavy_mass=1000.0, owner=False, counts=False, pixels=True, out=None):
@@ -908,9 +906,7 @@ class Engine:
 
     def render_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last render_bodies' two kernels (bh_render_kernel_ms)."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._lib.bh_render_kernel_ms(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self._lib.bh_render_kernel_ms)
 
     def set_tracers(self, x, y, vx=None, vy=None):
         """bh_set_tracers: replace the engine's tracer list -- massless test particles of mass
@@ -1021,9 +1017,7 @@ class Engine:
 
     def render_quads_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last render_quads' kernels (bh_render_quads_kernel_ms)."""
-        ms = ctypes.c_double(0.0)
-        self._check(self._lib.bh_render_quads_kernel_ms(self._h, ctypes.byref(ms)))
-        return ms.value
+        return self._kernel_ms(self._lib.bh_render_quads_kernel_ms)
 
     def let_stats(self):
         """Multi-rank build sharding: LET builds, full builds, last subset size, last LET nodes."""

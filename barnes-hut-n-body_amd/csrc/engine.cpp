@@ -123,6 +123,17 @@ struct bh_local_group {
     }
 };
 
+// The kernel stopwatch of a query (bh_*_kernel_ms): two events around its last launch, made on
+// first use.  `timed` is set once both were recorded; a failed call leaves the last reading.
+struct Stopwatch {
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool timed = false;
+    int start(bh_engine *e, hipStream_t s);
+    int stop(bh_engine *e, hipStream_t s);
+    int ms(double *out) const;  // 0.0 before the first launch
+    void destroy();
+};
+
 struct bh_engine {
     bh::Multi *multi = nullptr;  // a multi-device handle (multi.cpp): the members do the work
     // ... or, for a body list below multi_min bodies, one pipelined single-GPU engine on the first
@@ -222,8 +233,7 @@ struct bh_engine {
     double *phi = nullptr;        // the last bh_compute_potential's phi, slot order
     int64_t phi_cap = 0;
     double *diag_part = nullptr;  // the reductions' workgroup partials, then their 8 results
-    hipEvent_t pot_ev[2] = {nullptr, nullptr};  // around the last potential kernel
-    bool pot_timed = false;
+    Stopwatch pot_sw;             // around the last potential kernel launch
 
     // bh_compute_field (field.hip): the call's own probe buffers, allocated on first use and
     // grown when needed; nothing of the engine's state or bookkeeping is kept here
@@ -233,8 +243,7 @@ struct bh_engine {
     void *fld_scratch = nullptr;
     size_t fld_scratch_bytes = 0;
     int64_t fld_cap = 0;
-    hipEvent_t fld_ev[2] = {nullptr, nullptr};  // around the last field kernel
-    bool fld_timed = false;
+    Stopwatch fld_sw;  // around the last field kernel
 
     // bh_compute_field_direct / bh_compute_force_error (direct_field.hip): the targets' buffers,
     // the calls' own as bh_compute_field's are, allocated on first use and grown when needed
@@ -243,16 +252,14 @@ struct bh_engine {
     uint32_t *dfl_u32 = nullptr;      // the samples' caller indices, their slots
     uint32_t *dfl_slot_of = nullptr;  // caller index -> slot, dfl_slot_cap entries
     int64_t dfl_cap = 0, dfl_slot_cap = 0;
-    hipEvent_t dfl_ev[2] = {nullptr, nullptr};  // around the last k_direct_targets launch
-    bool dfl_timed = false;
+    Stopwatch dfl_sw;  // around the last k_direct_targets launch
 
     // bh_compute_field_grid (field.hip k_field_grid): result planes of its own, allocated on
     // first use and kept while nx * ny does not grow; there is nothing to upload
     double *fgr_out = nullptr;                 // ax, ay, phi planes of fgr_cap grid points
     bh_field_grid_stats *fgr_stats = nullptr;  // the reduction's partials, then its result
     int64_t fgr_cap = 0;
-    hipEvent_t fgr_ev[2] = {nullptr, nullptr};  // around the last k_field_grid launch
-    bool fgr_timed = false;
+    Stopwatch fgr_sw;  // around the last k_field_grid launch
 
     // bh_set_tracers (field.hip k_tracer_step): the tracer list and its lane map.  Nothing is
     // allocated while the list is empty; every buffer is sized for exactly trc_n tracers and made
@@ -277,8 +284,7 @@ struct bh_engine {
     uint8_t *rnd_pin = nullptr;  // pinned host bounce buffer of the staged planes
     size_t rnd_pin_bytes = 0;
     bool rnd_clean = false;
-    hipEvent_t rnd_ev[2] = {nullptr, nullptr};  // around the last render's two kernels
-    bool rnd_timed = false;
+    Stopwatch rnd_sw;  // around the last render's two kernels
 
     // bh_render_quads (render_quads.hip): buffers of its own, allocated on first use, kept while
     // the pixel count is unchanged.  The three working planes are zero between calls (the scans
@@ -288,8 +294,7 @@ struct bh_engine {
     unsigned long long *qd_count = nullptr;   // the cell count in partial sums, device
     size_t qd_pix = 0;  // pixels the planes above are sized for
     bool qd_clean = false;
-    hipEvent_t qd_ev[2] = {nullptr, nullptr};  // around the last call's kernels
-    bool qd_timed = false;
+    Stopwatch qd_sw;  // around the last call's kernels
 
     bool tree_valid = false;  // lastTree (BHA:304): keys_s / cpl / base / nodes are current
     // Multi-rank engines end a call with a LET build too; lastTree is then built on demand by
@@ -699,6 +704,49 @@ int dev_alloc(bh_engine *e, T *&ptr, size_t count) {
     HIPCHK(e, hipMalloc((void **)&ptr, count * sizeof(T)));
     return BH_OK;
 }
+
+// Grow-or-keep of buffers that share the capacity `cap`: false while `need` entries fit and the
+// buffers (`first`: one of them) exist.  Else the caller allocates them anew and then sets cap;
+// cap is 0 meanwhile, so after a failed allocation the next call allocates again.
+bool outgrown(int64_t &cap, const void *first, int64_t need) {
+    if (need <= cap && first) return false;
+    cap = 0;
+    return true;
+}
+
+}  // namespace
+
+int Stopwatch::start(bh_engine *e, hipStream_t s) {
+    for (hipEvent_t &v : ev)
+        if (!v) HIPCHK(e, hipEventCreate(&v));
+    HIPCHK(e, hipEventRecord(ev[0], s));
+    return BH_OK;
+}
+
+int Stopwatch::stop(bh_engine *e, hipStream_t s) {
+    HIPCHK(e, hipEventRecord(ev[1], s));
+    timed = true;
+    return BH_OK;
+}
+
+int Stopwatch::ms(double *out) const {
+    *out = 0.0;
+    if (!timed) return BH_OK;
+    float f = 0.f;
+    if (hipEventElapsedTime(&f, ev[0], ev[1]) != hipSuccess) return BH_E_DEVICE;
+    *out = (double)f;
+    return BH_OK;
+}
+
+void Stopwatch::destroy() {
+    for (hipEvent_t &v : ev) {
+        if (v) (void)hipEventDestroy(v);
+        v = nullptr;
+    }
+    timed = false;
+}
+
+namespace {
 
 int alloc_state(bh_engine *e, BodyState &s, size_t cap) {
     TRY(dev_alloc(e, s.x, cap));
@@ -1580,173 +1628,11 @@ int wave_order_next(bh_engine *e, int slot, int64_t lanes, hipStream_t s) {
     return BH_OK;
 }
 
-// bh_compute_potential's route through evaluate(): the tree exactly as for visits != null (a full
-// build or the carried one, never a LET, not sharded), then the potential of every body into
-// e->phi by slot in place of the forces; a2 is left alone.  run = false: build only (the members
-// of a multi-device handle past the first, whose replicas must take the same jitter).
-struct PotentialEval {
-    bool run;
-};
-
-int potential_bufs(bh_engine *e) {
-    if (e->phi_cap < e->cap || !e->phi) {
-        TRY(dev_alloc(e, e->phi, (size_t)e->cap));
-        e->phi_cap = e->cap;
-    }
-    if (!e->diag_part) TRY(dev_alloc(e, e->diag_part, diag_partial_doubles()));
-    for (hipEvent_t &ev : e->pot_ev)
-        if (!ev) HIPCHK(e, hipEventCreate(&ev));
-    return BH_OK;
-}
-
-// bh_compute_field's route through evaluate(): the tree exactly as for PotentialEval, then the
-// field at the caller's probes (host arrays; pm nullable) into e->fld_out by probe index.  run =
-// false or no probes: build only.  The probes live in buffers of the call's own (field_bufs).
-struct FieldEval {
-    bool run;
-    int64_t n_probe;
-    const double *px, *py, *pm;
-    // bh_compute_field_direct: every leaf of the tree's leaf sequence summed by the tiled kernel
-    // (direct_field.hip) into e->dfl_out, whatever theta is -- no cell is accepted
-    bool direct = false;
-    // bh_compute_field_grid: the probes are the points of *grid, formed by the kernel itself
-    // (n_probe, px, py, pm unused) into the planes of e->fgr_out that `planes` names (bit k: ax,
-    // ay, phi), then -- with stats -- their summary into e->fgr_stats
-    const bh_field_grid *grid = nullptr;
-    unsigned planes = 0;
-    bool stats = false;
-};
-
-int field_grid_bufs(bh_engine *e, int64_t points) {
-    if (points > e->fgr_cap || !e->fgr_out) {
-        e->fgr_cap = 0;
-        TRY(dev_alloc(e, e->fgr_out, 3 * (size_t)points));
-        e->fgr_cap = points;
-    }
-    if (!e->fgr_stats) TRY(dev_alloc(e, e->fgr_stats, field_grid_stat_partials()));
-    for (hipEvent_t &ev : e->fgr_ev)
-        if (!ev) HIPCHK(e, hipEventCreate(&ev));
-    return BH_OK;
-}
-
-// k_field_grid between its two events (d_T null: no tree -- no bodies), then the reduction.
-int field_grid_launch(bh_engine *e, const FieldEval &f, const Node *nodes, size_t node_cap,
-                      const uint32_t *d_T, const ForceParams &fp) {
-    const bh_field_grid &g = *f.grid;
-    const int64_t points = (int64_t)g.nx * g.ny;
-    TRY(field_grid_bufs(e, points));
-    const size_t cap = (size_t)e->fgr_cap;
-    double *out[3];
-    for (int k = 0; k < 3; ++k)
-        out[k] = (f.stats || (f.planes >> k & 1u)) ? e->fgr_out + k * cap : nullptr;
-    HIPCHK(e, hipEventRecord(e->fgr_ev[0], e->stream));
-    field_grid_walk(nodes, node_cap, d_T, g, e->geo, fp, out[0], out[1], out[2], e->stream);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->fgr_ev[1], e->stream));
-    e->fgr_timed = true;
-    if (f.stats) {
-        field_grid_stats(points, out[0], out[1], out[2], e->fgr_stats,
-                         e->fgr_stats + field_grid_stat_partials() - 1, e->stream);
-        HIPCHK(e, hipGetLastError());
-    }
-    return BH_OK;
-}
-
-int field_bufs(bh_engine *e, int64_t n_probe) {
-    if (n_probe > e->fld_cap || !e->fld_in) {
-        const size_t cap = (size_t)n_probe;
-        TRY(dev_alloc(e, e->fld_in, 3 * cap));
-        TRY(dev_alloc(e, e->fld_out, 3 * cap));
-        TRY(dev_alloc(e, e->fld_u32, 4 * cap));
-        if (e->fld_scratch) (void)hipFree(e->fld_scratch);
-        e->fld_scratch = nullptr;
-        e->fld_cap = 0;
-        e->fld_scratch_bytes = field_sort_bytes(n_probe);
-        HIPCHK(e, hipMalloc(&e->fld_scratch, e->fld_scratch_bytes ? e->fld_scratch_bytes : 1));
-        e->fld_cap = n_probe;
-    }
-    for (hipEvent_t &ev : e->fld_ev)
-        if (!ev) HIPCHK(e, hipEventCreate(&ev));
-    return BH_OK;
-}
-
-// Upload, key and sort the probes, then the field kernel between its two events (d_T null: no
-// tree -- no bodies).
-int field_launch(bh_engine *e, const FieldEval &f, const Node *nodes, size_t node_cap,
-                 const uint32_t *d_T, const ForceParams &fp) {
-    const int64_t P = f.n_probe;
-    TRY(field_bufs(e, P));
-    const size_t cap = (size_t)e->fld_cap, bytes = sizeof(double) * (size_t)P;
-    double *px = e->fld_in, *py = px + cap, *pm = f.pm ? py + cap : nullptr;
-    HIPCHK(e, hipMemcpyAsync(px, f.px, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(py, f.py, bytes, hipMemcpyHostToDevice, e->stream));
-    if (pm) HIPCHK(e, hipMemcpyAsync(pm, f.pm, bytes, hipMemcpyHostToDevice, e->stream));
-    uint32_t *key = e->fld_u32, *key_s = key + cap, *idx = key_s + cap, *order = idx + cap;
-    HIPCHK(e, field_order(P, px, py, e->geo, key, key_s, idx, order, e->fld_scratch,
-                          e->fld_scratch_bytes, e->stream));
-    HIPCHK(e, hipEventRecord(e->fld_ev[0], e->stream));
-    field_walk(nodes, node_cap, d_T, px, py, pm, order, P, e->geo, fp, e->fld_out,
-               e->fld_out + cap, e->fld_out + 2 * cap, e->stream);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->fld_ev[1], e->stream));
-    e->fld_timed = true;
-    return BH_OK;
-}
-
-int direct_field_bufs(bh_engine *e, int64_t n_target) {
-    if (n_target > e->dfl_cap || !e->dfl_in) {
-        const size_t cap = (size_t)n_target;
-        e->dfl_cap = 0;
-        TRY(dev_alloc(e, e->dfl_in, 3 * cap));
-        TRY(dev_alloc(e, e->dfl_out, 5 * cap));
-        TRY(dev_alloc(e, e->dfl_u32, 2 * cap));
-        e->dfl_cap = n_target;
-    }
-    for (hipEvent_t &ev : e->dfl_ev)
-        if (!ev) HIPCHK(e, hipEventCreate(&ev));
-    return BH_OK;
-}
-
-// Upload the probes, then k_direct_targets between its two events.  tree: the leaf sequence of
-// the engine's tree was just extracted (ensure_direct + leaf_list_build); else there is no tree
-// (no bodies) and every sum stays +0.0.
-int direct_field_launch(bh_engine *e, const FieldEval &f, bool tree, const ForceParams &fp) {
-    const int64_t P = f.n_probe;
-    TRY(direct_field_bufs(e, P));
-    const size_t cap = (size_t)e->dfl_cap, bytes = sizeof(double) * (size_t)P;
-    double *px = e->dfl_in, *py = px + cap, *pm = f.pm ? py + cap : nullptr;
-    HIPCHK(e, hipMemcpyAsync(px, f.px, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(py, f.py, bytes, hipMemcpyHostToDevice, e->stream));
-    if (pm) HIPCHK(e, hipMemcpyAsync(pm, f.pm, bytes, hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipEventRecord(e->dfl_ev[0], e->stream));
-    direct_targets(tree ? e->leaves : LeafList{nullptr}, tree ? e->leaf_count : nullptr, px, py, pm,
-                   nullptr, P, fp.G, fp.soft2, e->dfl_out, e->dfl_out + cap, e->dfl_out + 2 * cap,
-                   e->stream);
-    HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->dfl_ev[1], e->stream));
-    e->dfl_timed = true;
-    return BH_OK;
-}
-
-int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fused = nullptr,
-             bool allow_let = false, bool *let_used = nullptr,
-             const PotentialEval *pot = nullptr, const FieldEval *fld = nullptr) {
-    if (fused) *fused = false;
-    if (let_used) *let_used = false;
-    // (the pieces are ranges of the slot order: spatially compact only once a full build has
-    // put the state into Morton order -- after a reset it is the caller's order)
-    if (allow_let && !visits && (e->comm || e->group || e->solo) && let_active(e) &&
-        !theta2_is_zero(e) &&
-        e->st_morton && e->let_age < BH_LET_REFRESH) {
-        bool done = false;
-        TRY(evaluate_let(e, kick, &done));
-        if (done) {
-            ++e->let_age;
-            if (let_used) *let_used = true;
-            if (fused) *fused = true;  // integrated in the evaluation
-            return BH_OK;
-        }
-    }
+// The full tree of the current state, for a force evaluation or a query: the one the pipelined
+// step carried into this call (with its build's flags; its jitter becomes part of the state), or a
+// build now -- never a LET, not sharded.  Afterwards e->nodes, e->base[n] (the node count) and
+// e->st in the build's slot order are current on e->stream.
+int ensure_tree(bh_engine *e) {
     e->let_age = 0;
     const int64_t n = e->n;
     if (e->prebuilt) {  // the pipelined step built this tree (single GPU: nothing deferred)
@@ -1771,50 +1657,178 @@ int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fu
         }
         TRY(mark(e, 0));
     }
+    return BH_OK;
+}
+
+// The tree's non-empty leaves in pre-order into e->leaves (the all-pairs kernels' input).
+int build_leaf_list(bh_engine *e) {
+    TRY(ensure_direct(e));
+    HIPCHK(e, leaf_list_build(e->nodes, e->base + e->n, (int64_t)e->node_cap, e->leaf_flags,
+                              e->leaf_sel, e->leaf_count, e->leaves, e->n, e->leaf_cover,
+                              e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
+    return BH_OK;
+}
+
+// ---- the queries' launches --------------------------------------------------------------
+// Each runs on the tree ensure_tree() left (tree = false: no bodies, no tree -- every sum stays
+// +0.0), by this engine alone, into buffers of its own that are made on first use and grown when
+// needed, with its kernel between the two events of its stopwatch.  None touches a2, the state
+// or what the pipelined step carries into the next call.
+int potential_bufs(bh_engine *e) {
+    if (outgrown(e->phi_cap, e->phi, e->cap)) {
+        TRY(dev_alloc(e, e->phi, (size_t)e->cap));
+        e->phi_cap = e->cap;
+    }
+    if (!e->diag_part) TRY(dev_alloc(e, e->diag_part, diag_partial_doubles()));
+    return BH_OK;
+}
+
+// bh_compute_potential: the potential of every body into e->phi, by slot.
+int potential_launch(bh_engine *e) {
+    const int64_t n = e->n;
+    const ForceParams fp = force_params(e);
+    TRY(potential_bufs(e));
+    if (fp.theta2 == 0.0) {  // all pairs over the leaf sequence (direct.hip)
+        TRY(build_leaf_list(e));
+        TRY(e->pot_sw.start(e, e->stream));
+        direct_potential(e->leaves, e->leaf_count, e->st.x, e->st.y, e->st.cidx, n, fp.G, fp.soft2,
+                         e->phi, e->stream);
+    } else {
+        TRY(e->pot_sw.start(e, e->stream));
+        potential_walk(e->nodes, e->node_cap, e->base + n, e->st.x, e->st.y, e->st.cidx, n, e->geo,
+                       fp, e->phi, e->lanes_valid ? e->lanes : nullptr, e->stream);
+    }
+    HIPCHK(e, hipGetLastError());
+    return e->pot_sw.stop(e, e->stream);
+}
+
+// The caller's probes of bh_compute_field / bh_compute_field_direct (host arrays; pm nullable).
+struct Probes {
+    int64_t n;
+    const double *px, *py, *pm;
+};
+
+int upload_probes(bh_engine *e, const Probes &p, double *px, double *py, double *pm) {
+    const size_t bytes = sizeof(double) * (size_t)p.n;
+    HIPCHK(e, hipMemcpyAsync(px, p.px, bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(py, p.py, bytes, hipMemcpyHostToDevice, e->stream));
+    if (pm) HIPCHK(e, hipMemcpyAsync(pm, p.pm, bytes, hipMemcpyHostToDevice, e->stream));
+    return BH_OK;
+}
+
+// bh_compute_field: upload, key and sort the probes, then the field walk (theta = 0: the same
+// walk, which then opens every internal node) into e->fld_out by probe index.
+int field_launch(bh_engine *e, const Probes &p, bool tree) {
+    const int64_t P = p.n;
+    if (outgrown(e->fld_cap, e->fld_in, P)) {
+        const size_t cap = (size_t)P;
+        TRY(dev_alloc(e, e->fld_in, 3 * cap));   // px, py, pm
+        TRY(dev_alloc(e, e->fld_out, 3 * cap));  // ax, ay, phi
+        TRY(dev_alloc(e, e->fld_u32, 4 * cap));  // key, sorted key, index, order
+        if (e->fld_scratch) (void)hipFree(e->fld_scratch);
+        e->fld_scratch = nullptr;
+        e->fld_scratch_bytes = field_sort_bytes(P);
+        HIPCHK(e, hipMalloc(&e->fld_scratch, e->fld_scratch_bytes ? e->fld_scratch_bytes : 1));
+        e->fld_cap = P;
+    }
+    const size_t cap = (size_t)e->fld_cap;
+    double *px = e->fld_in, *py = px + cap, *pm = p.pm ? py + cap : nullptr;
+    TRY(upload_probes(e, p, px, py, pm));
+    uint32_t *key = e->fld_u32, *key_s = key + cap, *idx = key_s + cap, *order = idx + cap;
+    HIPCHK(e, field_order(P, px, py, e->geo, key, key_s, idx, order, e->fld_scratch,
+                          e->fld_scratch_bytes, e->stream));
+    TRY(e->fld_sw.start(e, e->stream));
+    field_walk(tree ? e->nodes : nullptr, tree ? e->node_cap : 0, tree ? e->base + e->n : nullptr,
+               px, py, pm, order, P, e->geo, force_params(e), e->fld_out, e->fld_out + cap,
+               e->fld_out + 2 * cap, e->stream);
+    HIPCHK(e, hipGetLastError());
+    return e->fld_sw.stop(e, e->stream);
+}
+
+// The targets' planes of k_direct_targets: tx, ty, tm; ax, ay, phi, ax_tree, ay_tree; the
+// samples' caller indices and their slots.
+int direct_field_bufs(bh_engine *e, int64_t n_target) {
+    if (outgrown(e->dfl_cap, e->dfl_in, n_target)) {
+        const size_t cap = (size_t)n_target;
+        TRY(dev_alloc(e, e->dfl_in, 3 * cap));
+        TRY(dev_alloc(e, e->dfl_out, 5 * cap));
+        TRY(dev_alloc(e, e->dfl_u32, 2 * cap));
+        e->dfl_cap = n_target;
+    }
+    return BH_OK;
+}
+
+// bh_compute_field_direct: every leaf of the tree's leaf sequence summed by the tiled kernel
+// (direct_field.hip) into e->dfl_out by probe index, whatever theta is -- no cell is accepted.
+int direct_field_launch(bh_engine *e, const Probes &p, bool tree) {
+    const int64_t P = p.n;
+    const ForceParams fp = force_params(e);
+    if (tree) TRY(build_leaf_list(e));
+    TRY(direct_field_bufs(e, P));
+    const size_t cap = (size_t)e->dfl_cap;
+    double *px = e->dfl_in, *py = px + cap, *pm = p.pm ? py + cap : nullptr;
+    TRY(upload_probes(e, p, px, py, pm));
+    TRY(e->dfl_sw.start(e, e->stream));
+    direct_targets(tree ? e->leaves : LeafList{nullptr}, tree ? e->leaf_count : nullptr, px, py, pm,
+                   nullptr, P, fp.G, fp.soft2, e->dfl_out, e->dfl_out + cap, e->dfl_out + 2 * cap,
+                   e->stream);
+    HIPCHK(e, hipGetLastError());
+    return e->dfl_sw.stop(e, e->stream);
+}
+
+// bh_compute_field_grid: the probes are the grid's points, formed by k_field_grid itself, into
+// the planes of e->fgr_out that `planes` names (bit k: ax, ay, phi; all three with stats), then
+// -- with stats -- their summary into e->fgr_stats.  There is nothing to upload.
+int field_grid_launch(bh_engine *e, const bh_field_grid &g, unsigned planes, bool stats,
+                      bool tree) {
+    const int64_t points = (int64_t)g.nx * g.ny;
+    if (outgrown(e->fgr_cap, e->fgr_out, points)) {
+        TRY(dev_alloc(e, e->fgr_out, 3 * (size_t)points));
+        e->fgr_cap = points;
+    }
+    if (!e->fgr_stats) TRY(dev_alloc(e, e->fgr_stats, field_grid_stat_partials()));
+    const size_t cap = (size_t)e->fgr_cap;
+    double *out[3];
+    for (int k = 0; k < 3; ++k)
+        out[k] = (stats || (planes >> k & 1u)) ? e->fgr_out + k * cap : nullptr;
+    TRY(e->fgr_sw.start(e, e->stream));
+    field_grid_walk(tree ? e->nodes : nullptr, tree ? e->node_cap : 0,
+                    tree ? e->base + e->n : nullptr, g, e->geo, force_params(e), out[0], out[1],
+                    out[2], e->stream);
+    HIPCHK(e, hipGetLastError());
+    TRY(e->fgr_sw.stop(e, e->stream));
+    if (stats) {
+        field_grid_stats(points, out[0], out[1], out[2], e->fgr_stats,
+                         e->fgr_stats + field_grid_stat_partials() - 1, e->stream);
+        HIPCHK(e, hipGetLastError());
+    }
+    return BH_OK;
+}
+
+int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fused = nullptr,
+             bool allow_let = false, bool *let_used = nullptr) {
+    if (fused) *fused = false;
+    if (let_used) *let_used = false;
+    // (the pieces are ranges of the slot order: spatially compact only once a full build has
+    // put the state into Morton order -- after a reset it is the caller's order)
+    if (allow_let && !visits && (e->comm || e->group || e->solo) && let_active(e) &&
+        !theta2_is_zero(e) &&
+        e->st_morton && e->let_age < BH_LET_REFRESH) {
+        bool done = false;
+        TRY(evaluate_let(e, kick, &done));
+        if (done) {
+            ++e->let_age;
+            if (let_used) *let_used = true;
+            if (fused) *fused = true;  // integrated in the evaluation
+            return BH_OK;
+        }
+    }
+    TRY(ensure_tree(e));
+    const int64_t n = e->n;
     ForceParams fp = force_params(e);  // BHA:378
     const uint32_t *d_T = e->base + n;
-    if (pot) {  // the potential on this tree, by this engine alone, over the whole list
-        if (!pot->run) return BH_OK;
-        TRY(potential_bufs(e));
-        if (fp.theta2 == 0.0) {  // all pairs over the leaf sequence (direct.hip)
-            TRY(ensure_direct(e));
-            HIPCHK(e, leaf_list_build(e->nodes, d_T, (int64_t)e->node_cap, e->leaf_flags,
-                                      e->leaf_sel, e->leaf_count, e->leaves, n, e->leaf_cover,
-                                      e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
-            HIPCHK(e, hipEventRecord(e->pot_ev[0], e->stream));
-            direct_potential(e->leaves, e->leaf_count, e->st.x, e->st.y, e->st.cidx, n, fp.G,
-                             fp.soft2, e->phi, e->stream);
-        } else {
-            HIPCHK(e, hipEventRecord(e->pot_ev[0], e->stream));
-            potential_walk(e->nodes, e->node_cap, d_T, e->st.x, e->st.y, e->st.cidx, n, e->geo, fp,
-                           e->phi, e->lanes_valid ? e->lanes : nullptr, e->stream);
-        }
-        HIPCHK(e, hipGetLastError());
-        HIPCHK(e, hipEventRecord(e->pot_ev[1], e->stream));
-        e->pot_timed = true;
-        return BH_OK;
-    }
-    if (fld) {  // the field at the probes on this tree, by this engine alone (theta = 0: the
-                // same walk, which then opens every internal node)
-        if (fld->run && fld->grid)  // the grid's points, formed on the device (k_field_grid)
-            return field_grid_launch(e, *fld, e->nodes, e->node_cap, d_T, fp);
-        if (!fld->run || fld->n_probe == 0) return BH_OK;
-        if (fld->direct) {  // every leaf, by the tiled kernel (direct_field.hip)
-            TRY(ensure_direct(e));
-            HIPCHK(e, leaf_list_build(e->nodes, d_T, (int64_t)e->node_cap, e->leaf_flags,
-                                      e->leaf_sel, e->leaf_count, e->leaves, n, e->leaf_cover,
-                                      e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
-            return direct_field_launch(e, *fld, true, fp);
-        }
-        return field_launch(e, *fld, e->nodes, e->node_cap, d_T, fp);
-    }
     const bool direct = fp.theta2 == 0.0 && !visits;
-    if (direct) {
-        TRY(ensure_direct(e));
-        HIPCHK(e, leaf_list_build(e->nodes, d_T, (int64_t)e->node_cap, e->leaf_flags, e->leaf_sel,
-                                  e->leaf_count, e->leaves, n, e->leaf_cover, e->leaf_tmp,
-                                  e->leaf_tmp_bytes, e->stream));
-    }
+    if (direct) TRY(build_leaf_list(e));
     const TraverseCounters counters{visits, e->contrib32, e->wave_iters, e->wave_blocks};
     const uint32_t *lanes = e->lanes_valid ? e->lanes : nullptr;  // [lo, hi): lane ranges
     e->a2_lanes = direct ? nullptr : lanes;
@@ -1902,6 +1916,31 @@ int check_tree_flags(bh_engine *e) {
         e->err = "jitter replay reached an unsupported geometry (body stayed inside a depth J+1 cell)";
         return BH_E_STATE;
     }
+    return BH_OK;
+}
+
+// The frame of a call that evaluates on the full tree without stepping (bh_compute_*), on one
+// engine.  query_begin: the call is counted, the device current, the phase marks and the tree
+// flags cleared.  Between the two the call enqueues on e->stream: ensure_tree() or evaluate()
+// unless there are no bodies, then its own kernels.  query_end, had_tree: the tree's jitter is in
+// the state (the mirror is stale), the stream is waited for and the build's flags are checked --
+// only then may results be copied out; either way the phase timings are collected.
+int query_begin(bh_engine *e) {
+    e->prog_api.store(++e->api_calls);
+    HIPCHK(e, hipSetDevice(e->device));
+    e->ev_used = 0;
+    e->timings_pending = false;
+    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
+    return BH_OK;
+}
+
+int query_end(bh_engine *e, bool had_tree) {
+    if (had_tree) {
+        e->mir_fresh = false;
+        SYNC(e, e->stream);
+        TRY(check_tree_flags(e));
+    }
+    if (e->profiling) TRY(collect_timings(e));
     return BH_OK;
 }
 
@@ -3127,6 +3166,36 @@ int comm_refused(bh_engine *e) {
 }  // namespace
 #define COMM_GUARD(e) TRY(comm_refused(e))
 
+// A tree query, written as query(engine, run), on the handle the caller holds.  Every member of a
+// multi-device handle runs it -- each builds, so that the build jitters every replica alike --
+// and member 0 alone evaluates and answers (run = true); any other engine is its own member 0.
+// Each engine passes its guards first, and a failure marks a multi-rank engine failed.
+namespace {
+int query_call(bh_engine *e, const std::function<int(bh_engine *, bool)> &query) {
+    auto guarded = [&](bh_engine *m, int r) -> int {
+        ASYNC_GUARD(m);
+        COMM_GUARD(m);
+        return fail_multi_rank(m, query(m, r == 0));
+    };
+    return e->multi ? multi_fan(e, guarded, false) : guarded(e, 0);
+}
+
+// A list argument of `fn`: the count `what` = n must be in [0, 2^28] and, unless it is 0, the
+// arrays that `arrays` names must be there (have).
+int check_list(bh_engine *e, const char *fn, const char *what, int64_t n, bool have,
+               const char *arrays) {
+    if (n < 0 || n > ((int64_t)1 << 28)) {
+        e->err = std::string(fn) + ": " + what + " must be in [0, 2^28]";
+        return BH_E_INVALID;
+    }
+    if (n > 0 && !have) {
+        e->err = std::string(fn) + ": " + arrays + " is NULL";
+        return BH_E_INVALID;
+    }
+    return BH_OK;
+}
+}  // namespace
+
 // =========================================================================================
 extern "C" {
 
@@ -3362,18 +3431,8 @@ void bh_destroy(bh_engine *e) {
                     e->trc, e->trc_snap, e->trc_u32, e->trc_scratch};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
-    for (hipEvent_t ev : e->fgr_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->pot_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->fld_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->dfl_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->rnd_ev)
-        if (ev) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : e->qd_ev)
-        if (ev) (void)hipEventDestroy(ev);
+    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->rnd_sw, &e->qd_sw})
+        sw->destroy();
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
     if (e->pin) (void)hipHostFree(e->pin);
@@ -3868,51 +3927,43 @@ int bh_compute_accelerations(bh_engine *e, double *ax, double *ay, int64_t *visi
 }
 
 static int compute_accelerations_rank(bh_engine *e, double *ax, double *ay, int64_t *visits) {
-    e->prog_api.store(++e->api_calls);
-    HIPCHK(e, hipSetDevice(e->device));
+    TRY(query_begin(e));
     const int64_t n = e->n;
-    e->ev_used = 0;
-    e->timings_pending = false;
-    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
-    if (n > 0) {
-        TRY(evaluate(e, visits ? e->visits32 : nullptr));
-        e->mir_fresh = false;
-        scatter_acc_to_caller(n, e->st.cidx, e->a2, e->ax, e->ay, e->stream, e->a2_lanes,
-                              e->a2_layout);
-        HIPCHK(e, hipGetLastError());
-        SYNC(e, e->stream);
-        TRY(check_tree_flags(e));
-        if (ax) HIPCHK(e, hipMemcpy(ax, e->ax, sizeof(double) * n, hipMemcpyDeviceToHost));
-        if (ay) HIPCHK(e, hipMemcpy(ay, e->ay, sizeof(double) * n, hipMemcpyDeviceToHost));
-        if (visits) {
-            std::vector<uint32_t> v((size_t)n), c((size_t)n);
-            HIPCHK(e, hipMemcpy(v.data(), e->visits32, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-            HIPCHK(e, hipMemcpy(c.data(), e->st.cidx, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-            int64_t lane_sum = 0;
-            for (int64_t i = 0; i < n; ++i) {
-                visits[c[(size_t)i]] = v[(size_t)i];
-                lane_sum += v[(size_t)i];
-            }
-            HIPCHK(e, hipMemcpy(v.data(), e->contrib32, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
-            int64_t contrib_sum = 0;
-            for (int64_t i = 0; i < n; ++i) contrib_sum += v[(size_t)i];
-            const int64_t waves = (n + 63) / 64;
-            std::vector<uint32_t> wi((size_t)waves), wb((size_t)waves);
-            HIPCHK(e, hipMemcpy(wi.data(), e->wave_iters, sizeof(uint32_t) * waves,
-                                hipMemcpyDeviceToHost));
-            HIPCHK(e, hipMemcpy(wb.data(), e->wave_blocks, sizeof(uint32_t) * waves,
-                                hipMemcpyDeviceToHost));
-            int64_t wsum = 0, bsum = 0;
-            for (uint32_t w : wi) wsum += w;
-            for (uint32_t w : wb) bsum += w;
-            e->stat_lane_visits = lane_sum;
-            e->stat_lane_contrib = contrib_sum;
-            e->stat_wave_iters = wsum;
-            e->stat_wave_blocks = bsum;
-            e->stat_waves = waves;
+    if (n == 0) return query_end(e, false);
+    TRY(evaluate(e, visits ? e->visits32 : nullptr));
+    scatter_acc_to_caller(n, e->st.cidx, e->a2, e->ax, e->ay, e->stream, e->a2_lanes,
+                          e->a2_layout);
+    HIPCHK(e, hipGetLastError());
+    TRY(query_end(e, true));
+    if (ax) HIPCHK(e, hipMemcpy(ax, e->ax, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (ay) HIPCHK(e, hipMemcpy(ay, e->ay, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (visits) {
+        std::vector<uint32_t> v((size_t)n), c((size_t)n);
+        HIPCHK(e, hipMemcpy(v.data(), e->visits32, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        HIPCHK(e, hipMemcpy(c.data(), e->st.cidx, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        int64_t lane_sum = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            visits[c[(size_t)i]] = v[(size_t)i];
+            lane_sum += v[(size_t)i];
         }
+        HIPCHK(e, hipMemcpy(v.data(), e->contrib32, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+        int64_t contrib_sum = 0;
+        for (int64_t i = 0; i < n; ++i) contrib_sum += v[(size_t)i];
+        const int64_t waves = (n + 63) / 64;
+        std::vector<uint32_t> wi((size_t)waves), wb((size_t)waves);
+        HIPCHK(e, hipMemcpy(wi.data(), e->wave_iters, sizeof(uint32_t) * waves,
+                            hipMemcpyDeviceToHost));
+        HIPCHK(e, hipMemcpy(wb.data(), e->wave_blocks, sizeof(uint32_t) * waves,
+                            hipMemcpyDeviceToHost));
+        int64_t wsum = 0, bsum = 0;
+        for (uint32_t w : wi) wsum += w;
+        for (uint32_t w : wb) bsum += w;
+        e->stat_lane_visits = lane_sum;
+        e->stat_lane_contrib = contrib_sum;
+        e->stat_wave_iters = wsum;
+        e->stat_wave_blocks = bsum;
+        e->stat_waves = waves;
     }
-    if (e->profiling) TRY(collect_timings(e));
     return BH_OK;
 }
 
@@ -3955,57 +4006,43 @@ static int diagnostics_state(bh_engine *e, bool with_phi, bh_diagnostics *out) {
 }
 
 // bh_compute_potential / bh_compute_diagnostics(with_potential) on one engine, state semantics of
-// compute_accelerations_rank.  run: this engine evaluates (else it only builds); phi (nullable):
-// caller-order copy-out; diag (nullable): the reductions on the state after the build.
-static int potential_rank(bh_engine *e, double *phi, bool run, bh_diagnostics *diag) {
-    e->prog_api.store(++e->api_calls);
-    HIPCHK(e, hipSetDevice(e->device));
+// compute_accelerations_rank.  run: this engine evaluates and answers (else it only builds); phi
+// (nullable): caller-order copy-out; diag (nullable): the reductions on the state after the build.
+static int potential_rank(bh_engine *e, bool run, double *phi, bh_diagnostics *diag) {
+    TRY(query_begin(e));
     const int64_t n = e->n;
-    e->ev_used = 0;
-    e->timings_pending = false;
-    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
     if (n > 0) {
-        const PotentialEval pe{run};
-        TRY(evaluate(e, nullptr, KICK_NONE, nullptr, false, nullptr, &pe));
-        e->mir_fresh = false;
+        TRY(ensure_tree(e));
+        if (run) TRY(potential_launch(e));
         if (run && phi) {
             const double *ps[1] = {e->phi};
             double *pd[1] = {e->ax};
             scatter_to_caller(n, e->st.cidx, 1, ps, pd, e->stream);
             HIPCHK(e, hipGetLastError());
         }
-        SYNC(e, e->stream);
-        TRY(check_tree_flags(e));
-        if (run && phi)
-            HIPCHK(e, hipMemcpy(phi, e->ax, sizeof(double) * n, hipMemcpyDeviceToHost));
     }
-    if (diag) TRY(diagnostics_state(e, run && n > 0, diag));
-    if (e->profiling) TRY(collect_timings(e));
+    TRY(query_end(e, n > 0));
+    if (run && phi && n > 0)
+        HIPCHK(e, hipMemcpy(phi, e->ax, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (run && diag) TRY(diagnostics_state(e, n > 0, diag));
     return BH_OK;
-}
-
-static int potential_call(bh_engine *e, double *phi, bool run, bh_diagnostics *diag) {
-    ASYNC_GUARD(e);
-    COMM_GUARD(e);
-    return fail_multi_rank(e, potential_rank(e, phi, run, diag));
 }
 
 int bh_compute_potential(bh_engine *e, double *phi) {
     if (!e) return BH_E_INVALID;
     ASYNC_GUARD(e);
-    // (every member builds -- the build may jitter every replica alike; member 0 evaluates and
-    // hands the result out)
-    MULTI_ALL(e, potential_call(m_, r_ == 0 ? phi : nullptr, r_ == 0, nullptr));
-    return potential_call(e, phi, true, nullptr);
+    return query_call(e, [&](bh_engine *m, bool run) {
+        return potential_rank(m, run, phi, nullptr);
+    });
 }
 
 int bh_compute_diagnostics(bh_engine *e, int with_potential, bh_diagnostics *out) {
     if (!e || !out) return BH_E_INVALID;
     ASYNC_GUARD(e);
-    if (with_potential) {
-        MULTI_ALL(e, potential_call(m_, nullptr, r_ == 0, r_ == 0 ? out : nullptr));
-        return potential_call(e, nullptr, true, out);
-    }
+    if (with_potential)
+        return query_call(e, [&](bh_engine *m, bool run) {
+            return potential_rank(m, run, nullptr, out);
+        });
     if (e->multi) {  // reductions only: member 0's replica (complete at the API boundary)
         const int rc = bh_compute_diagnostics(MULTI_M0(e), 0, out);
         if (rc != BH_OK) e->err = bh_last_error(MULTI_M0(e));
@@ -4015,115 +4052,66 @@ int bh_compute_diagnostics(bh_engine *e, int with_potential, bh_diagnostics *out
     return diagnostics_state(e, false, out);
 }
 
-int bh_potential_kernel_ms(const bh_engine *e, double *ms) {
+// bh_*_kernel_ms of the stopwatch `sw`: the active engine's member 0 launched it.
+static int kernel_ms(const bh_engine *e, Stopwatch bh_engine::*sw, double *ms) {
     if (!e || !ms) return BH_E_INVALID;
-    e = MULTI_M0(e);
-    *ms = 0.0;
-    if (!e->pot_timed) return BH_OK;
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, e->pot_ev[0], e->pot_ev[1]) != hipSuccess) return BH_E_DEVICE;
-    *ms = (double)f;
-    return BH_OK;
+    return (MULTI_M0(e)->*sw).ms(ms);
 }
 
-// bh_compute_field on one engine, state semantics of compute_accelerations_rank.  run: this
-// engine evaluates the probes (else it only builds); ax, ay, phi (each nullable): copy-out in the
-// caller's probe order.  With fe.grid the probes are the grid's points, the planes row-major, and
-// stats (nullable) receives their summary.
-static int field_rank(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi,
-                      bh_field_grid_stats *stats = nullptr) {
-    e->prog_api.store(++e->api_calls);
-    HIPCHK(e, hipSetDevice(e->device));
-    const int64_t n = e->n, P = fe.grid ? (int64_t)fe.grid->nx * fe.grid->ny : fe.n_probe;
-    const bool run = fe.run && P > 0;
-    e->ev_used = 0;
-    e->timings_pending = false;
-    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
-    if (n > 0) {
-        TRY(evaluate(e, nullptr, KICK_NONE, nullptr, false, nullptr, nullptr, &fe));
-        e->mir_fresh = false;
-        SYNC(e, e->stream);
-        TRY(check_tree_flags(e));
-    } else if (run) {  // no bodies, no tree: every sum stays +0.0
-        const ForceParams fp = force_params(e);
-        if (fe.grid)
-            TRY(field_grid_launch(e, fe, nullptr, 0, nullptr, fp));
-        else if (fe.direct)
-            TRY(direct_field_launch(e, fe, false, fp));
-        else
-            TRY(field_launch(e, fe, nullptr, 0, nullptr, fp));
-        SYNC(e, e->stream);
-    }
-    if (run) {
-        const size_t cap = (size_t)(fe.grid ? e->fgr_cap : fe.direct ? e->dfl_cap : e->fld_cap);
-        const size_t bytes = sizeof(double) * (size_t)P;
-        const double *res = fe.grid ? e->fgr_out : fe.direct ? e->dfl_out : e->fld_out;
-        double *out[3] = {ax, ay, phi};
-        for (int k = 0; k < 3; ++k)
-            if (out[k]) HIPCHK(e, hipMemcpy(out[k], res + k * cap, bytes, hipMemcpyDeviceToHost));
-        if (stats)
-            HIPCHK(e, hipMemcpy(stats, e->fgr_stats + field_grid_stat_partials() - 1,
-                                sizeof(*stats), hipMemcpyDeviceToHost));
-    }
-    if (e->profiling) TRY(collect_timings(e));
-    return BH_OK;
+int bh_potential_kernel_ms(const bh_engine *e, double *ms) {
+    return kernel_ms(e, &bh_engine::pot_sw, ms);
 }
 
-static int field_call(bh_engine *e, const FieldEval &fe, double *ax, double *ay, double *phi,
-                      bh_field_grid_stats *stats = nullptr) {
-    ASYNC_GUARD(e);
-    COMM_GUARD(e);
-    return fail_multi_rank(e, field_rank(e, fe, ax, ay, phi, stats));
+// A field query on one engine, state semantics of compute_accelerations_rank.  run: this engine
+// evaluates by launch(tree) (else it only builds); the caller then copies the results out.
+static int field_rank(bh_engine *e, bool run, const std::function<int(bool)> &launch) {
+    TRY(query_begin(e));
+    const bool tree = e->n > 0;
+    if (tree) TRY(ensure_tree(e));
+    if (run) TRY(launch(tree));
+    if (run && !tree) SYNC(e, e->stream);  // no bodies, no tree: every sum stays +0.0
+    return query_end(e, tree);
+}
+
+// The planes of P results at `res`, stride `cap`, to ax, ay, phi (each nullable).
+static int field_copy_out(bh_engine *e, const double *res, int64_t cap, int64_t P, double *ax,
+                          double *ay, double *phi) {
+    double *out[3] = {ax, ay, phi};
+    for (int k = 0; k < 3; ++k)
+        if (out[k])
+            HIPCHK(e, hipMemcpy(out[k], res + k * (size_t)cap, sizeof(double) * (size_t)P,
+                                hipMemcpyDeviceToHost));
+    return BH_OK;
 }
 
 int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const double *py,
                      const double *pm, double *ax, double *ay, double *phi) {
     if (!e) return BH_E_INVALID;
     ASYNC_GUARD(e);
-    if (n_probe < 0 || n_probe > ((int64_t)1 << 28)) {
-        e->err = "bh_compute_field: n_probe must be in [0, 2^28]";
-        return BH_E_INVALID;
-    }
-    if (n_probe > 0 && (!px || !py)) {
-        e->err = "bh_compute_field: px or py is NULL";
-        return BH_E_INVALID;
-    }
-    const FieldEval all{true, n_probe, px, py, pm}, none{false, 0, nullptr, nullptr, nullptr};
-    // (every member builds, member 0 evaluates and answers: as bh_compute_potential)
-    MULTI_ALL(e, r_ == 0 ? field_call(m_, all, ax, ay, phi)
-                         : field_call(m_, none, nullptr, nullptr, nullptr));
-    return field_call(e, all, ax, ay, phi);
+    TRY(check_list(e, "bh_compute_field", "n_probe", n_probe, px && py, "px or py"));
+    const Probes p{n_probe, px, py, pm};
+    return query_call(e, [&](bh_engine *m, bool run) {
+        if (p.n == 0) run = false;
+        TRY(field_rank(m, run, [&](bool tree) { return field_launch(m, p, tree); }));
+        return run ? field_copy_out(m, m->fld_out, m->fld_cap, p.n, ax, ay, phi) : BH_OK;
+    });
 }
 
 int bh_field_kernel_ms(const bh_engine *e, double *ms) {
-    if (!e || !ms) return BH_E_INVALID;
-    e = MULTI_M0(e);
-    *ms = 0.0;
-    if (!e->fld_timed) return BH_OK;
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, e->fld_ev[0], e->fld_ev[1]) != hipSuccess) return BH_E_DEVICE;
-    *ms = (double)f;
-    return BH_OK;
+    return kernel_ms(e, &bh_engine::fld_sw, ms);
 }
 
 int bh_compute_field_direct(bh_engine *e, int64_t n_probe, const double *px, const double *py,
                             const double *pm, double *ax, double *ay, double *phi) {
     if (!e) return BH_E_INVALID;
     ASYNC_GUARD(e);
-    if (n_probe < 0 || n_probe > ((int64_t)1 << 28)) {
-        e->err = "bh_compute_field_direct: n_probe must be in [0, 2^28]";
-        return BH_E_INVALID;
-    }
-    if (n_probe > 0 && (!px || !py)) {
-        e->err = "bh_compute_field_direct: px or py is NULL";
-        return BH_E_INVALID;
-    }
-    const FieldEval all{true, n_probe, px, py, pm, true};
-    const FieldEval none{false, 0, nullptr, nullptr, nullptr, true};
-    // (every member builds, member 0 evaluates and answers: as bh_compute_field)
-    MULTI_ALL(e, r_ == 0 ? field_call(m_, all, ax, ay, phi)
-                         : field_call(m_, none, nullptr, nullptr, nullptr));
-    return field_call(e, all, ax, ay, phi);
+    TRY(check_list(e, "bh_compute_field_direct", "n_probe", n_probe, px && py, "px or py"));
+    const Probes p{n_probe, px, py, pm};
+    return query_call(e, [&](bh_engine *m, bool run) {
+        if (p.n == 0) run = false;
+        TRY(field_rank(m, run, [&](bool tree) { return direct_field_launch(m, p, tree); }));
+        return run ? field_copy_out(m, m->dfl_out, m->dfl_cap, p.n, ax, ay, phi) : BH_OK;
+    });
 }
 
 // bh_compute_force_error's summary of the four sample arrays (include/bh_engine.h): sequential,
@@ -4156,85 +4144,69 @@ static void force_error_summary(int64_t k, const double *axt, const double *ayt,
     }
 }
 
-// What bh_compute_force_error asks of one engine.  run = false: the evaluation alone (the members
-// of a multi-device handle past the first).  idx: the validated caller indices.
+// What bh_compute_force_error asks of the engine that answers.  idx: the validated caller indices.
 struct ForceErrorArgs {
-    bool run;
     int64_t k;
     const uint32_t *idx;
     double *axt, *ayt, *axe, *aye;
     bh_force_error *out;
 };
 
-// compute_accelerations_rank's evaluation, then -- on the same tree, in the same call -- the
-// samples' exact accelerations by k_direct_targets in body mode over the tree's leaf sequence.
-static int force_error_rank(bh_engine *e, const ForceErrorArgs &fa) {
-    e->prog_api.store(++e->api_calls);
-    HIPCHK(e, hipSetDevice(e->device));
+// The samples' exact accelerations on the tree of the evaluation just enqueued, by
+// k_direct_targets in body mode over the tree's leaf sequence; their tree accelerations (e->ax,
+// e->ay by caller index) are gathered beside them.
+static int force_error_launch(bh_engine *e, const ForceErrorArgs &fa) {
     const int64_t n = e->n, K = fa.k;
-    const bool run = fa.run && K > 0 && n > 0;  // (K > 0 with n = 0 was refused: no valid index)
-    e->ev_used = 0;
-    e->timings_pending = false;
-    HIPCHK(e, hipMemsetAsync(e->scalars + 1, 0, sizeof(uint32_t), e->stream));
+    const ForceParams fp = force_params(e);
+    TRY(build_leaf_list(e));
+    TRY(direct_field_bufs(e, K));
+    if (outgrown(e->dfl_slot_cap, e->dfl_slot_of, n)) {
+        TRY(dev_alloc(e, e->dfl_slot_of, (size_t)e->cap));
+        e->dfl_slot_cap = e->cap;
+    }
+    const size_t cap = (size_t)e->dfl_cap;
+    double *tx = e->dfl_in, *ty = tx + cap, *tm = ty + cap;
+    uint32_t *idx = e->dfl_u32, *tslot = idx + cap;
+    HIPCHK(e, hipMemcpyAsync(idx, fa.idx, sizeof(uint32_t) * (size_t)K, hipMemcpyHostToDevice,
+                             e->stream));
+    HIPCHK(e, direct_body_targets(n, e->st, idx, K, e->dfl_slot_of, e->ax, e->ay, tx, ty, tm, tslot,
+                                  e->dfl_out + 3 * cap, e->dfl_out + 4 * cap, e->stream));
+    TRY(e->dfl_sw.start(e, e->stream));
+    direct_targets(e->leaves, e->leaf_count, tx, ty, tm, tslot, K, fp.G, fp.soft2, e->dfl_out,
+                   e->dfl_out + cap, nullptr, e->stream);
+    HIPCHK(e, hipGetLastError());
+    return e->dfl_sw.stop(e, e->stream);
+}
+
+// compute_accelerations_rank's evaluation, then -- on the same tree, in the same call, run: by
+// this engine -- force_error_launch and the answer (else the evaluation alone).
+static int force_error_rank(bh_engine *e, bool run, const ForceErrorArgs &fa) {
+    TRY(query_begin(e));
+    const int64_t n = e->n, K = fa.k;
+    const bool launch = run && K > 0 && n > 0;  // (K > 0 with n = 0 was refused: no valid index)
     if (n > 0) {
         TRY(evaluate(e, nullptr));
-        e->mir_fresh = false;
         scatter_acc_to_caller(n, e->st.cidx, e->a2, e->ax, e->ay, e->stream, e->a2_lanes,
                               e->a2_layout);
         HIPCHK(e, hipGetLastError());
-        if (run) {
-            const ForceParams fp = force_params(e);
-            TRY(ensure_direct(e));
-            HIPCHK(e, leaf_list_build(e->nodes, e->base + n, (int64_t)e->node_cap, e->leaf_flags,
-                                      e->leaf_sel, e->leaf_count, e->leaves, n, e->leaf_cover,
-                                      e->leaf_tmp, e->leaf_tmp_bytes, e->stream));
-            TRY(direct_field_bufs(e, K));
-            if (e->dfl_slot_cap < n || !e->dfl_slot_of) {
-                e->dfl_slot_cap = 0;
-                TRY(dev_alloc(e, e->dfl_slot_of, (size_t)e->cap));
-                e->dfl_slot_cap = e->cap;
-            }
-            const size_t cap = (size_t)e->dfl_cap;
-            double *tx = e->dfl_in, *ty = tx + cap, *tm = ty + cap;
-            uint32_t *idx = e->dfl_u32, *tslot = idx + cap;
-            HIPCHK(e, hipMemcpyAsync(idx, fa.idx, sizeof(uint32_t) * (size_t)K,
-                                     hipMemcpyHostToDevice, e->stream));
-            HIPCHK(e, direct_body_targets(n, e->st, idx, K, e->dfl_slot_of, e->ax, e->ay, tx, ty, tm,
-                                          tslot, e->dfl_out + 3 * cap, e->dfl_out + 4 * cap,
-                                          e->stream));
-            HIPCHK(e, hipEventRecord(e->dfl_ev[0], e->stream));
-            direct_targets(e->leaves, e->leaf_count, tx, ty, tm, tslot, K, fp.G, fp.soft2,
-                           e->dfl_out, e->dfl_out + cap, nullptr, e->stream);
-            HIPCHK(e, hipGetLastError());
-            HIPCHK(e, hipEventRecord(e->dfl_ev[1], e->stream));
-            e->dfl_timed = true;
-        }
-        SYNC(e, e->stream);
-        TRY(check_tree_flags(e));
+        if (launch) TRY(force_error_launch(e, fa));
     }
-    if (fa.run) {
-        std::vector<double> h((size_t)(4 * K));
-        double *host[4] = {h.data(), h.data() + K, h.data() + 2 * K, h.data() + 3 * K};
-        if (run) {
-            const size_t cap = (size_t)e->dfl_cap, bytes = sizeof(double) * (size_t)K;
-            const int plane[4] = {3, 4, 0, 1};  // ax_tree, ay_tree, ax_exact, ay_exact
-            for (int q = 0; q < 4; ++q)
-                HIPCHK(e, hipMemcpy(host[q], e->dfl_out + plane[q] * cap, bytes,
-                                    hipMemcpyDeviceToHost));
-        }
-        double *user[4] = {fa.axt, fa.ayt, fa.axe, fa.aye};
+    TRY(query_end(e, n > 0));
+    if (!run) return BH_OK;
+    std::vector<double> h((size_t)(4 * K));
+    double *host[4] = {h.data(), h.data() + K, h.data() + 2 * K, h.data() + 3 * K};
+    if (launch) {
+        const size_t cap = (size_t)e->dfl_cap, bytes = sizeof(double) * (size_t)K;
+        const int plane[4] = {3, 4, 0, 1};  // ax_tree, ay_tree, ax_exact, ay_exact
         for (int q = 0; q < 4; ++q)
-            if (user[q] && K > 0) std::memcpy(user[q], host[q], sizeof(double) * (size_t)K);
-        if (fa.out) force_error_summary(K, host[0], host[1], host[2], host[3], fa.out);
+            HIPCHK(e, hipMemcpy(host[q], e->dfl_out + plane[q] * cap, bytes,
+                                hipMemcpyDeviceToHost));
     }
-    if (e->profiling) TRY(collect_timings(e));
+    double *user[4] = {fa.axt, fa.ayt, fa.axe, fa.aye};
+    for (int q = 0; q < 4; ++q)
+        if (user[q] && K > 0) std::memcpy(user[q], host[q], sizeof(double) * (size_t)K);
+    if (fa.out) force_error_summary(K, host[0], host[1], host[2], host[3], fa.out);
     return BH_OK;
-}
-
-static int force_error_call(bh_engine *e, const ForceErrorArgs &fa) {
-    ASYNC_GUARD(e);
-    COMM_GUARD(e);
-    return fail_multi_rank(e, force_error_rank(e, fa));
 }
 
 int bh_compute_force_error(bh_engine *e, int64_t n_sample, const int64_t *idx, double *ax_tree,
@@ -4242,14 +4214,7 @@ int bh_compute_force_error(bh_engine *e, int64_t n_sample, const int64_t *idx, d
                            bh_force_error *out) {
     if (!e) return BH_E_INVALID;
     ASYNC_GUARD(e);
-    if (n_sample < 0 || n_sample > ((int64_t)1 << 28)) {
-        e->err = "bh_compute_force_error: n_sample must be in [0, 2^28]";
-        return BH_E_INVALID;
-    }
-    if (n_sample > 0 && !idx) {
-        e->err = "bh_compute_force_error: idx is NULL";
-        return BH_E_INVALID;
-    }
+    TRY(check_list(e, "bh_compute_force_error", "n_sample", n_sample, idx != nullptr, "idx"));
     const int64_t n = bh_num_bodies(e);
     std::vector<uint32_t> idx32((size_t)n_sample);
     for (int64_t j = 0; j < n_sample; ++j) {
@@ -4260,23 +4225,13 @@ int bh_compute_force_error(bh_engine *e, int64_t n_sample, const int64_t *idx, d
         }
         idx32[(size_t)j] = (uint32_t)idx[j];
     }
-    const ForceErrorArgs all{true, n_sample, idx32.data(), ax_tree, ay_tree, ax_exact, ay_exact,
-                             out};
-    const ForceErrorArgs none{false, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    const ForceErrorArgs fa{n_sample, idx32.data(), ax_tree, ay_tree, ax_exact, ay_exact, out};
     // (every member evaluates as bh_compute_accelerations does; member 0 does the rest)
-    MULTI_ALL(e, force_error_call(m_, r_ == 0 ? all : none));
-    return force_error_call(e, all);
+    return query_call(e, [&](bh_engine *m, bool run) { return force_error_rank(m, run, fa); });
 }
 
 int bh_direct_field_kernel_ms(const bh_engine *e, double *ms) {
-    if (!e || !ms) return BH_E_INVALID;
-    e = MULTI_M0(e);
-    *ms = 0.0;
-    if (!e->dfl_timed) return BH_OK;
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, e->dfl_ev[0], e->dfl_ev[1]) != hipSuccess) return BH_E_DEVICE;
-    *ms = (double)f;
-    return BH_OK;
+    return kernel_ms(e, &bh_engine::dfl_sw, ms);
 }
 
 int bh_direct_field_shape(int64_t n_target, int64_t *out3) {
@@ -4316,23 +4271,21 @@ int bh_compute_field_grid(bh_engine *e, const bh_field_grid *g, double *ax, doub
     }
     const bh_field_grid grid = *g;
     const unsigned planes = (ax ? 1u : 0u) | (ay ? 2u : 0u) | (phi ? 4u : 0u);
-    const FieldEval all{true, 0, nullptr, nullptr, nullptr, false, &grid, planes, stats != nullptr};
-    const FieldEval none{false, 0, nullptr, nullptr, nullptr};
-    // (every member builds, member 0 evaluates and answers: as bh_compute_field)
-    MULTI_ALL(e, r_ == 0 ? field_call(m_, all, ax, ay, phi, stats)
-                         : field_call(m_, none, nullptr, nullptr, nullptr));
-    return field_call(e, all, ax, ay, phi, stats);
+    return query_call(e, [&](bh_engine *m, bool run) {
+        TRY(field_rank(m, run, [&](bool tree) {
+            return field_grid_launch(m, grid, planes, stats != nullptr, tree);
+        }));
+        if (!run) return BH_OK;
+        TRY(field_copy_out(m, m->fgr_out, m->fgr_cap, (int64_t)grid.nx * grid.ny, ax, ay, phi));
+        if (stats)  // the planes are row-major; their summary is the last of the partials
+            HIPCHK(m, hipMemcpy(stats, m->fgr_stats + field_grid_stat_partials() - 1,
+                                sizeof(*stats), hipMemcpyDeviceToHost));
+        return BH_OK;
+    });
 }
 
 int bh_field_grid_kernel_ms(const bh_engine *e, double *ms) {
-    if (!e || !ms) return BH_E_INVALID;
-    e = MULTI_M0(e);
-    *ms = 0.0;
-    if (!e->fgr_timed) return BH_OK;
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, e->fgr_ev[0], e->fgr_ev[1]) != hipSuccess) return BH_E_DEVICE;
-    *ms = (double)f;
-    return BH_OK;
+    return kernel_ms(e, &bh_engine::fgr_sw, ms);
 }
 
 int bh_field_grid_shape(int32_t nx, int32_t ny, int64_t *out4) {
@@ -4392,8 +4345,6 @@ static int render_buffers(bh_engine *e, size_t pad, bool pixels, bool owner, boo
             HIPCHK(e, hipMemsetAsync(e->rnd_cnt, 0, sizeof(uint32_t) * pad, e->stream));
         e->rnd_clean = true;
     }
-    for (hipEvent_t &ev : e->rnd_ev)
-        if (!ev) HIPCHK(e, hipEventCreate(&ev));
     return BH_OK;
 }
 
@@ -4413,7 +4364,7 @@ static int render_state(bh_engine *e, const bh_view &v, uint8_t *pixels, uint32_
     TRY(render_buffers(e, pad, pixels != nullptr, owner != nullptr, counts != nullptr));
     const BodyState &s = e->view_pending ? e->view : e->st;  // (not the prebuilt tree's jitter)
     e->rnd_clean = false;
-    HIPCHK(e, hipEventRecord(e->rnd_ev[0], e->stream));
+    TRY(e->rnd_sw.start(e, e->stream));
     render_raster(n, s.x, s.y, s.m, s.cidx, v, e->rnd_packed, counts ? e->rnd_cnt : nullptr,
                   e->stream);
     HIPCHK(e, hipGetLastError());
@@ -4421,9 +4372,8 @@ static int render_state(bh_engine *e, const bh_view &v, uint8_t *pixels, uint32_
                    pixels ? e->rnd_pixels : nullptr, owner ? e->rnd_owner : nullptr,
                    counts ? e->rnd_counts : nullptr, e->stream);
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->rnd_ev[1], e->stream));
+    TRY(e->rnd_sw.stop(e, e->stream));
     e->rnd_clean = true;
-    e->rnd_timed = true;
     // BH_RENDER_PINNED=1: through a pinned bounce buffer and a host copy (A/B, read per call)
     const char *env = std::getenv("BH_RENDER_PINNED");
     const bool pinned = env && std::atoi(env) != 0;
@@ -4478,28 +4428,14 @@ int bh_render_bodies(bh_engine *e, const bh_view *v, uint8_t *pixels, uint32_t *
 }
 
 int bh_render_kernel_ms(const bh_engine *e, double *ms) {
-    if (!e || !ms) return BH_E_INVALID;
-    e = MULTI_M0(e);
-    *ms = 0.0;
-    if (!e->rnd_timed) return BH_OK;
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, e->rnd_ev[0], e->rnd_ev[1]) != hipSuccess) return BH_E_DEVICE;
-    *ms = (double)f;
-    return BH_OK;
+    return kernel_ms(e, &bh_engine::rnd_sw, ms);
 }
 
 int bh_set_tracers(bh_engine *e, int64_t n, const double *x, const double *y, const double *vx,
                    const double *vy) {
     if (!e) return BH_E_INVALID;
     ASYNC_GUARD(e);
-    if (n < 0 || n > ((int64_t)1 << 28)) {
-        e->err = "bh_set_tracers: n must be in [0, 2^28]";
-        return BH_E_INVALID;
-    }
-    if (n > 0 && (!x || !y)) {
-        e->err = "bh_set_tracers: x or y is NULL";
-        return BH_E_INVALID;
-    }
+    TRY(check_list(e, "bh_set_tracers", "n", n, x && y, "x or y"));
     if (e->multi || e->comm || e->group || e->solo) {
         if (n == 0) return BH_OK;  // (such an engine never holds tracers)
         e->err = "bh_set_tracers: tracers need the one-GPU engine (bh_create): this engine's steps "
@@ -4675,8 +4611,6 @@ static int quads_buffers(bh_engine *e, size_t npix, bool image, bool direct) {
         }
     }
     if (!e->qd_count) TRY(dev_alloc(e, e->qd_count, (size_t)QUADS_COUNT_WORDS));
-    for (hipEvent_t &ev : e->qd_ev)
-        if (!ev) HIPCHK(e, hipEventCreate(&ev));
     return BH_OK;
 }
 
@@ -4698,13 +4632,12 @@ static int render_quads_state(bh_engine *e, const bh_view &v, uint32_t *lines, i
     unsigned long long part[QUADS_COUNT_WORDS];
     HIPCHK(e, hipMemsetAsync(e->qd_count, 0, sizeof(part), e->stream));
     if (lines) e->qd_clean = false;
-    HIPCHK(e, hipEventRecord(e->qd_ev[0], e->stream));
+    TRY(e->qd_sw.start(e, e->stream));
     quads_render(t, e->geo, v, e->qd_rowd, e->qd_cold, direct ? e->qd_dir : nullptr, combine,
                  lines ? e->qd_out : nullptr, e->qd_count, e->stream);
     HIPCHK(e, hipGetLastError());
-    HIPCHK(e, hipEventRecord(e->qd_ev[1], e->stream));
+    TRY(e->qd_sw.stop(e, e->stream));
     if (lines) e->qd_clean = true;
-    e->qd_timed = true;
     if (lines)
         HIPCHK(e, hipMemcpyAsync(lines, e->qd_out, sizeof(uint32_t) * npix, hipMemcpyDeviceToHost,
                                  e->stream));
@@ -4739,14 +4672,7 @@ int bh_render_quads(bh_engine *e, const bh_view *v, uint32_t *lines, int64_t *n_
 }
 
 int bh_render_quads_kernel_ms(const bh_engine *e, double *ms) {
-    if (!e || !ms) return BH_E_INVALID;
-    e = MULTI_M0(e);
-    *ms = 0.0;
-    if (!e->qd_timed) return BH_OK;
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, e->qd_ev[0], e->qd_ev[1]) != hipSuccess) return BH_E_DEVICE;
-    *ms = (double)f;
-    return BH_OK;
+    return kernel_ms(e, &bh_engine::qd_sw, ms);
 }
 
 int bh_last_removed(const bh_engine *e, int64_t *idx, int64_t cap, int64_t *n_out) {
