@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "bh_field_grid_shape",
     "bh_set_tracers", "bh_num_tracers", "bh_get_tracers", "bh_tracer_kernel_ms",
     "bh_tracer_launch_shape", "bh_render_tracers",
+    "bh_set_step_log", "bh_get_step_log", "bh_get_step_log_phi", "bh_step_log_kernel_ms",
 )
 
 
@@ -86,6 +87,15 @@ class BhDiagnostics(ctypes.Structure):
         ("lz", ctypes.c_double),
         ("kinetic", ctypes.c_double),
         ("potential", ctypes.c_double),
+    ]
+
+
+class BhStepRecord(ctypes.Structure):
+    """struct bh_step_record (include/bh_engine.h) -- one record of the step log."""
+    _fields_ = [
+        ("step", ctypes.c_int64),
+        ("t", ctypes.c_double),
+        ("d", BhDiagnostics),
     ]
 
 
@@ -188,6 +198,15 @@ class Diagnostics:
         return self.kinetic + self.potential
 
 
+@dataclass(frozen=True)
+class StepRecord:
+    """One record of Engine.get_step_log(): the step's number since the log was enabled, the sum
+    of the logged steps' dt, and the Diagnostics of the state after the step's second kick."""
+    step: int
+    t: float
+    d: Diagnostics
+
+
 class BhError(RuntimeError):
     def __init__(self, rc, msg):
         super().__init__(f"bh_engine error {rc}: {msg}")
@@ -280,6 +299,10 @@ def load_library(path: str | None = None):
     lib.bh_get_tracers.argtypes = [_VP, _D, _D, _D, _D, ctypes.c_int64, _I64P]
     lib.bh_tracer_kernel_ms.argtypes = [_VP, _D, _I64P]
     lib.bh_tracer_launch_shape.argtypes = [ctypes.c_int64, _I64P]
+    lib.bh_set_step_log.argtypes = [_VP, ctypes.c_int64]
+    lib.bh_get_step_log.argtypes = [_VP, ctypes.POINTER(BhStepRecord), ctypes.c_int64, _I64P]
+    lib.bh_get_step_log_phi.argtypes = [_VP, _D, ctypes.c_int64, _I64P]
+    lib.bh_step_log_kernel_ms.argtypes = [_VP, _D, _I64P]
     lib.bh_render_tracers.argtypes = [_VP, ctypes.POINTER(BhView),
                                       ctypes.POINTER(ctypes.c_uint32),
                                       ctypes.POINTER(ctypes.c_uint32)]
@@ -945,6 +968,48 @@ class Engine:
         ms = ctypes.c_double(0.0)
         k = ctypes.c_int64(0)
         self._check(self._lib.bh_tracer_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(k)))
+        return ms.value, k.value
+
+    def set_step_log(self, capacity: int):
+        """bh_set_step_log: a ring of `capacity` records (1..2**20) that every step of every
+        step() call appends its conservation read-out to, on the device and without a host wait;
+        the ring starts empty with step and t at 0.  0: off, buffers freed.  One-GPU engines only
+        (BH_E_STATE otherwise, unless capacity is 0)."""
+        self._check(self._lib.bh_set_step_log(self._h, int(capacity)))
+
+    def get_step_log(self):
+        """bh_get_step_log: the logged records, oldest first, as a list of StepRecord(step, t, d)
+        -- d the Diagnostics of the state after the step's second kick and before its merge rule,
+        the potential from the step's own second traversal."""
+        n = ctypes.c_int64(0)
+        rc = self._lib.bh_get_step_log(self._h, None, 0, ctypes.byref(n))
+        if rc not in (0, -4):  # (BH_E_CAPACITY: the count)
+            self._check(rc)
+        recs = (BhStepRecord * max(n.value, 1))()
+        self._check(self._lib.bh_get_step_log(self._h, recs, n.value, ctypes.byref(n)))
+        return [StepRecord(int(r.step), r.t,
+                           Diagnostics(int(r.d.n), r.d.mass, r.d.mx, r.d.my, r.d.px, r.d.py, r.d.lz,
+                                       r.d.kinetic, r.d.potential))
+                for r in recs[:n.value]]
+
+    def get_step_log_phi(self):
+        """bh_get_step_log_phi: phi of every body of the last logged step, in the order of that
+        step's list (before its merge rule).  BH_E_STATE if no step was logged since the log was
+        enabled or the bodies were replaced."""
+        n = ctypes.c_int64(0)
+        rc = self._lib.bh_get_step_log_phi(self._h, None, 0, ctypes.byref(n))
+        if rc not in (0, -4):
+            self._check(rc)
+        phi = np.empty(max(n.value, 0), dtype=np.float64)
+        self._check(self._lib.bh_get_step_log_phi(self._h, _dp(phi), len(phi), ctypes.byref(n)))
+        return phi
+
+    def step_log_kernel_ms(self):
+        """(average HIP-event ms per step, steps) of the log's staging and reduction in the last
+        step() call (bh_step_log_kernel_ms); (0.0, 0) unless set_profiling(True)."""
+        ms = ctypes.c_double(0.0)
+        k = ctypes.c_int64(0)
+        self._check(self._lib.bh_step_log_kernel_ms(self._h, ctypes.byref(ms), ctypes.byref(k)))
         return ms.value, k.value
 
     def render_tracers(self, view_x=0.0, view_y=0.0, zoom=1.0, width=None, height=None,

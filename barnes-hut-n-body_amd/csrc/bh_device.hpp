@@ -424,8 +424,10 @@ struct WaveOrder {
     uint32_t *cost = nullptr;
 };
 size_t wave_order_runs(int64_t n);  // runs of a launch over n lanes (0: too many to order)
-// Whether traverse() walks [lo, hi) breadth first, one body per wave (traverse.hip bfs_walk)
-bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting);
+// Whether traverse() walks [lo, hi) breadth first, one body per wave (traverse.hip bfs_walk);
+// pot: the step log's kick-only walk with the potential, always the cursor walk
+bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
+                     bool pot = false);
 hipError_t wave_order(const uint32_t *cost, int64_t n, uint32_t *order, hipStream_t s);
 // What traverse() launches for [lo, hi) (host-only; traverse() itself launches from it, and
 // bh_launch_plan reports it).  ordered: a WaveOrder with an order is passed.
@@ -440,7 +442,7 @@ struct TraverseShape {
     uint32_t xcd_full;  // whole groups of workgroups that k_traverse remaps across the XCDs
 };
 TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
-                             bool ordered);
+                             bool ordered, bool pot = false);
 // The cursor walk's grouping for a launch of `lanes` lanes: bodies per wave (fewer than 64 for
 // small launches) and waves per workgroup (traverse_shape's own choices; field.hip launches by
 // them too).
@@ -450,7 +452,9 @@ void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x
               const double *m, const uint32_t *cidx, int64_t lo, int64_t hi, const Geometry &g,
               const ForceParams &fp, double *a2, const TraverseCounters *cnt,
               hipStream_t s, const KickArgs *kick = nullptr, const uint32_t *lanes = nullptr,
-              const WaveOrder *wo = nullptr);
+              const WaveOrder *wo = nullptr, double *phi = nullptr);
+// phi (non-null only with kick->mode == KICK_ONLY and cnt == nullptr: the step log): the walk also
+// writes phi[slot] = bh_compute_potential's phi of the body on this tree, 0.0 for a tombstone.
 // multi-GPU shard pieces (bh_shard_range): `rounds` x `world` pieces of whole wavefronts
 __host__ __device__ inline int64_t shard_sub(int64_t n, int world, int rounds) {
     const int64_t parts = (int64_t)world * rounds;
@@ -650,6 +654,16 @@ void potential_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, con
 size_t diag_partial_doubles();
 void diag_reduce(int64_t n, const double *x, const double *y, const double *vx, const double *vy,
                  const double *m, const double *phi, double *part, double *out8, hipStream_t s);
+
+// ---- launchers (step_log.hip): one record of the step log (bh_set_step_log) ----------------
+// diag_reduce over the first n planes' entries with n known only on the device -- n = pos[n0 - 1] +
+// keep[n0 - 1], the survivors of mirror_index over n0 caller indices (n0 = 0: n = 0) -- in
+// diag_reduce's own partition and trees for that n, then the record {step, t, {n, sums}} with
+// potential = 0.5 * sum m phi into `rec` (88 bytes, the layout of bh_step_record).  stage: the six
+// planes x, y, vx, vy, m, phi at stride `stride`; part: diag_partial_doubles() entries.
+void step_log_record(int64_t n0, const uint32_t *keep, const uint32_t *pos, const double *stage,
+                     int64_t stride, double *part, int64_t step, double t, void *rec,
+                     hipStream_t s);
 
 // ---- launchers (field.hip) -------------------------------------------------------
 // The field at n probe points that are not in the tree (bh_compute_field): probe j = (px[j],

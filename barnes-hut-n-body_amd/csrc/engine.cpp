@@ -274,6 +274,27 @@ struct bh_engine {
     double trc_ms_sum = 0.0;            // the tracer walks of the last bh_step call (profiling)
     int64_t trc_launches = 0;
 
+    // bh_set_step_log (step_log.hip): a device ring of slog_cap records (0: off, nothing allocated)
+    // and buffers of its own, sized for slog_bcap bodies: the logged walk's phi by slot, the six
+    // planes x, y, vx, vy, m, phi of the last logged step in list order (never e->alt: the pipelined
+    // step is using it), the survivors' index and the reduction's partials.  Everything the host
+    // needs for a record -- its ring slot, step and t -- it knows when it enqueues the step
+    void *slog_ring = nullptr;
+    int64_t slog_cap = 0;
+    int64_t slog_head = 0;   // records written since the ring was last emptied (slot = head % cap)
+    int64_t slog_step = 0;   // steps logged since bh_set_step_log enabled the log
+    double slog_t = 0.0;     // their dt, added in step order
+    int64_t slog_call_head = 0, slog_call_step = 0;  // at the start of the running bh_step call
+    double slog_call_t = 0.0;                        // (a replay and a failed call go back there)
+    double *slog_phi = nullptr, *slog_stage = nullptr, *slog_part = nullptr;
+    uint32_t *slog_keep = nullptr, *slog_pos = nullptr;
+    void *slog_tmp = nullptr;
+    size_t slog_tmp_bytes = 0;
+    int64_t slog_bcap = 0;
+    bool slog_phi_valid = false;  // slog_stage holds the planes of the ring's newest record
+    double slog_ms_sum = 0.0;     // the staging and reduction of the last bh_step call (profiling)
+    int64_t slog_launches = 0;
+
     // bh_render_bodies (render.hip): buffers of its own, allocated on first use, kept while the
     // padded pixel count is unchanged.  rnd_packed / rnd_cnt are zero between calls (the resolve
     // kernel re-zeroes what the rasteriser touched); rnd_clean = false: a call failed in between
@@ -872,6 +893,7 @@ TreeBuffers tree_buffers(bh_engine *e) {
 // ---- profiling events ----------------------------------------------------------------
 constexpr int PHASE_START = -2;         // mark(): a start marker even right behind another mark
 constexpr int PHASE_TRACERS = kPhases;  // mark(): the interval was a tracer walk (phase [1])
+constexpr int PHASE_STEP_LOG = kPhases + 1;  // ... the step log's staging and reduction (phase [2])
 int mark(bh_engine *e, int phase) {  // close the interval of `phase` begun at the last mark
     if (!e->profiling) return BH_OK;
     // phases are contiguous on the stream: the previous phase's end mark starts the next one
@@ -905,6 +927,8 @@ int collect_timings(bh_engine *e) {
     e->trav_samples.clear();
     e->trc_ms_sum = 0.0;
     e->trc_launches = 0;
+    e->slog_ms_sum = 0.0;
+    e->slog_launches = 0;
     for (size_t i = 1; i < e->ev_used; ++i) {
         int ph = e->ev_phase[i];
         if (ph < 0) continue;
@@ -914,6 +938,12 @@ int collect_timings(bh_engine *e) {
             e->phase_ms[1] += ms;
             e->trc_ms_sum += ms;
             ++e->trc_launches;
+            continue;
+        }
+        if (ph == PHASE_STEP_LOG) {  // a step's record: under the integration's phase
+            e->phase_ms[2] += ms;
+            e->slog_ms_sum += ms;
+            ++e->slog_launches;
             continue;
         }
         e->phase_ms[ph] += ms;
@@ -2182,6 +2212,72 @@ int tracer_restore(bh_engine *e) {
     return BH_OK;
 }
 
+// ---- the step log (bh_set_step_log) ------------------------------------------------------
+void step_log_free(bh_engine *e, bool ring) {
+    for (void **q : {(void **)&e->slog_phi, (void **)&e->slog_stage, (void **)&e->slog_part,
+                     (void **)&e->slog_keep, (void **)&e->slog_pos, &e->slog_tmp}) {
+        if (*q) (void)hipFree(*q);
+        *q = nullptr;
+    }
+    e->slog_tmp_bytes = 0;
+    e->slog_bcap = 0;
+    e->slog_phi_valid = false;
+    if (ring) {
+        if (e->slog_ring) (void)hipFree(e->slog_ring);
+        e->slog_ring = nullptr;
+        e->slog_cap = 0;
+    }
+}
+
+// The log's per-body buffers for the engine's body capacity (before a call's first step).
+int step_log_bufs(bh_engine *e) {
+    if (e->slog_cap <= 0 || (e->slog_bcap >= e->cap && e->slog_part)) return BH_OK;
+    step_log_free(e, false);
+    const size_t c = (size_t)std::max<int64_t>(e->cap, 1);
+    TRY(dev_alloc(e, e->slog_phi, c));
+    TRY(dev_alloc(e, e->slog_stage, 6 * c));
+    TRY(dev_alloc(e, e->slog_keep, c));
+    TRY(dev_alloc(e, e->slog_pos, c));
+    TRY(dev_alloc(e, e->slog_part, diag_partial_doubles()));
+    e->slog_tmp_bytes = compact_scratch_bytes((int64_t)c);
+    HIPCHK(e, hipMalloc(&e->slog_tmp, e->slog_tmp_bytes ? e->slog_tmp_bytes : 1));
+    e->slog_bcap = (int64_t)c;
+    return BH_OK;
+}
+
+// One step's record, enqueued on the engine's stream behind the step's second kick: e->slog_phi
+// holds the potential of every slot on the tree that evaluation walked; cidx and m are the flags
+// and masses that evaluation read (before the step's merge rule).  The bodies of the step's list
+// -- the slots without a tombstone, by caller index -- go to the log's planes in list order and
+// are reduced there; the record lands in the ring's next slot.  No host wait, no host copy.
+int step_log_step(bh_engine *e, const uint32_t *cidx, const double *m) {
+    if (e->slog_cap <= 0) return BH_OK;
+    const int64_t n = e->n, c = e->slog_bcap;
+    hipStream_t s = e->stream;
+    TRY(mark(e, PHASE_START));
+    if (n > 0) {
+        HIPCHK(e, mirror_index(n, cidx, e->slog_keep, e->slog_pos, e->slog_tmp, e->slog_tmp_bytes,
+                               s));
+        double *st = e->slog_stage;
+        const double *s5[5] = {e->st.x, e->st.y, e->st.vx, e->st.vy, m};
+        double *d5[5] = {st, st + c, st + 2 * c, st + 3 * c, st + 4 * c};
+        mirror_scatter(n, cidx, e->slog_pos, 5, s5, d5, s);
+        const double *s1[1] = {e->slog_phi};
+        double *d1[1] = {st + 5 * c};
+        mirror_scatter(n, cidx, e->slog_pos, 1, s1, d1, s);
+    }
+    e->slog_step += 1;
+    e->slog_t += e->p.dt;
+    char *slot = static_cast<char *>(e->slog_ring) +
+                 sizeof(bh_step_record) * (size_t)(e->slog_head % e->slog_cap);
+    e->slog_head += 1;
+    step_log_record(n, e->slog_keep, e->slog_pos, e->slog_stage, c, e->slog_part, e->slog_step,
+                    e->slog_t, slot, s);
+    HIPCHK(e, hipGetLastError());
+    e->slog_phi_valid = true;
+    return mark(e, PHASE_STEP_LOG);
+}
+
 // Copy of the state at the start of a bh_step call that may merge: if a step's candidate
 // pairs overflow the mailbox, the call is replayed from here with a larger one, so the rule
 // (BHA:478-520) holds for any number of pairs.
@@ -2221,6 +2317,9 @@ int restore(bh_engine *e) {
     e->vel_perm = nullptr;  // (the snapshot is complete)
     TRY(copy_state(e, e->snap, e->st, e->snap_n));
     TRY(tracer_restore(e));
+    e->slog_head = e->slog_call_head;  // a replayed call logs each step once
+    e->slog_step = e->slog_call_step;
+    e->slog_t = e->slog_call_t;
     e->n = e->snap_n;
     TRY(drop_carried_flags(e));
     e->prebuilt = false;
@@ -2600,11 +2699,17 @@ int evaluate_pipelined(bh_engine *e, bool last) {
     }
     WaveOrder wo;
     TRY(wave_order_for(e, 0, n, s, wo));
+    // (with the step log on: the same walk with every body's potential, by slot)
     traverse(e->nodes, e->node_cap, e->T_trav, e->st.x, e->st.y, e->m_trav, e->cidx_trav, 0, n,
-             e->geo, fp, e->a2, nullptr, s, &ka, lanes ? e->lanes_trav : nullptr, &wo);
+             e->geo, fp, e->a2, nullptr, s, &ka, lanes ? e->lanes_trav : nullptr, &wo,
+             e->slog_cap > 0 ? e->slog_phi : nullptr);
     HIPCHK(e, hipGetLastError());
     TRY(mark(e, 1));
     TRY(wave_order_next(e, 0, n, s));
+    // the step's record from the traversal's own copies of masses and flags (the merge rule --
+    // before the traversal on the mirror's early path, beside it otherwise -- writes st.m and
+    // st.cidx) and the positions and kicked velocities in st, on this stream before the swap
+    TRY(step_log_step(e, e->cidx_trav, e->m_trav));
     // the tracers on the tree and node count the traversal just read (the overlapped chain
     // writes the other node array, the masses and the flags: none of them read here)
     TRY(tracer_walk(e, e->nodes, e->node_cap, e->T_trav, KICK_ONLY));
@@ -2752,11 +2857,23 @@ int step_once(bh_engine *e, bool last) {
             TRY(mark(e, 2));
         }
         TRY(tracer_walk(e, e->nodes, e->node_cap, e->base + n, KICK_ONLY));
+        if (e->slog_cap > 0) {  // (one GPU, not pipelined: theta = 0, the all-pairs evaluation)
+            if (!theta2_is_zero(e)) {
+                e->err = "step log: a tree walk outside the pipelined step";
+                return BH_E_STATE;
+            }
+            // the potential over the evaluation's leaf list (bit-identical to the walk at theta 0)
+            direct_potential(e->leaves, e->leaf_count, e->st.x, e->st.y, e->st.cidx, n, e->p.G,
+                             e->p.soft2, e->slog_phi, e->stream);
+            HIPCHK(e, hipGetLastError());
+            TRY(step_log_step(e, e->st.cidx, e->st.m));
+        }
         e->tree_valid = !let2;  // lastTree = root (BHA:435)
         e->lazy_tree = lazy && let2;
     } else {  // no bodies, no tree: every sum is +0.0 and the tracers drift on straight lines
         TRY(tracer_walk(e, nullptr, 0, nullptr, KICK_DRIFT));
         TRY(tracer_walk(e, nullptr, 0, nullptr, KICK_ONLY));
+        TRY(step_log_step(e, nullptr, nullptr));  // an all-zero record: step and t advance
     }
     if (last)  // the call's removal count before its last merge rule (finish_merges, BHA:526)
         HIPCHK(e, hipMemcpyAsync(e->scalars + 8, e->scalars + 2, sizeof(uint32_t),
@@ -3428,7 +3545,8 @@ void bh_destroy(bh_engine *e) {
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
                     e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch,
                     e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats,
-                    e->trc, e->trc_snap, e->trc_u32, e->trc_scratch};
+                    e->trc, e->trc_snap, e->trc_u32, e->trc_scratch, e->slog_ring, e->slog_phi,
+                    e->slog_stage, e->slog_part, e->slog_keep, e->slog_pos, e->slog_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->rnd_sw, &e->qd_sw})
@@ -3561,6 +3679,7 @@ int bh_reset_bodies(bh_engine *e, int64_t n, const double *x, const double *y, c
     e->n = n;
     e->heavy_possible = true;
     e->removed.clear();
+    e->slog_phi_valid = false;  // (the log itself runs on)
     e->tree_valid = false;  // BHA:348
     e->lazy_tree = false;
     e->prebuilt = false;    // other bodies: the pipelined call's next tree is void
@@ -3594,7 +3713,16 @@ static int step_call(bh_engine *e, int32_t k) {
     MULTI_ALL(e, bh_step(m_, k));  // every GPU's share of every step, joined (BHA:374-395, 408)
     COMM_GUARD(e);
     e->prog_busy.store(1);
+    e->slog_call_head = e->slog_head;
+    e->slog_call_step = e->slog_step;
+    e->slog_call_t = e->slog_t;
     const int rc = fail_multi_rank(e, step_call_rank(e, k));
+    if (rc != BH_OK) {  // a failed call leaves an empty log; step and t as before the call
+        e->slog_head = 0;
+        e->slog_step = e->slog_call_step;
+        e->slog_t = e->slog_call_t;
+        e->slog_phi_valid = false;
+    }
     e->prog_busy.store(0);
     return rc;
 }
@@ -3604,6 +3732,9 @@ static int step_call_rank(bh_engine *e, int32_t k) {
     HIPCHK(e, hipSetDevice(e->device));
     e->trc_ms_sum = 0.0;  // bh_tracer_kernel_ms: this call's walks, timed only while profiling
     e->trc_launches = 0;
+    e->slog_ms_sum = 0.0;  // bh_step_log_kernel_ms likewise
+    e->slog_launches = 0;
+    if (k > 0) TRY(step_log_bufs(e));
     const bool may_merge = k > 0 && e->n > 1 && e->p.merge_min_dist > 0.0 && e->heavy_possible;
     // a multi-rank call with LET builds may have to be replayed with a larger subset capacity
     const bool may_let = k > 0 && e->n > 0 && (e->comm || e->group || e->solo) && let_active(e) &&
@@ -4497,6 +4628,89 @@ int bh_tracer_kernel_ms(const bh_engine *e, double *avg_ms, int64_t *launches) {
     if (e->async_running && std::this_thread::get_id() != e->step_thr.get_id()) return BH_E_STATE;
     *avg_ms = e->trc_launches ? e->trc_ms_sum / (double)e->trc_launches : 0.0;
     if (launches) *launches = e->trc_launches;
+    return BH_OK;
+}
+
+int bh_set_step_log(bh_engine *e, int64_t capacity) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    if (capacity < 0 || capacity > ((int64_t)1 << 20)) {
+        e->err = "bh_set_step_log: capacity must be in [0, 2^20]";
+        return BH_E_INVALID;
+    }
+    if (e->multi || e->comm || e->group || e->solo) {
+        if (capacity == 0) return BH_OK;  // (such an engine never holds a log)
+        e->err = "bh_set_step_log: the step log needs the one-GPU engine (bh_create): this engine's "
+                 "steps shard their builds as locally essential trees, which are not full trees -- "
+                 "no walk of one gives a body its full potential";
+        return BH_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    SYNC(e, e->stream);
+    step_log_free(e, true);
+    e->slog_head = e->slog_step = 0;
+    e->slog_t = 0.0;
+    if (capacity == 0) return BH_OK;
+    HIPCHK(e, hipMalloc(&e->slog_ring, sizeof(bh_step_record) * (size_t)capacity));
+    e->slog_cap = capacity;
+    return BH_OK;
+}
+
+int bh_get_step_log(bh_engine *e, bh_step_record *out, int64_t cap, int64_t *n_out) {
+    if (!e || !n_out || (!out && cap > 0)) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    const int64_t n = std::min(e->slog_head, e->slog_cap);
+    *n_out = n;
+    if (cap < n) return BH_E_CAPACITY;
+    if (n == 0) return BH_OK;
+    HIPCHK(e, hipSetDevice(e->device));
+    SYNC(e, e->stream);
+    // oldest first: the ring's tail from the next slot to write, then its head
+    const bh_step_record *ring = static_cast<const bh_step_record *>(e->slog_ring);
+    const int64_t first = e->slog_head > e->slog_cap ? e->slog_head % e->slog_cap : 0;
+    const int64_t a = std::min(n, e->slog_cap - first);
+    HIPCHK(e, hipMemcpy(out, ring + first, sizeof(bh_step_record) * (size_t)a,
+                        hipMemcpyDeviceToHost));
+    if (n > a)
+        HIPCHK(e, hipMemcpy(out + a, ring, sizeof(bh_step_record) * (size_t)(n - a),
+                            hipMemcpyDeviceToHost));
+    return BH_OK;
+}
+
+int bh_get_step_log_phi(bh_engine *e, double *phi, int64_t cap, int64_t *n_out) {
+    if (!e || !n_out || (!phi && cap > 0)) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    *n_out = 0;
+    if (e->slog_cap <= 0) return BH_OK;  // no log: nothing to return
+    if (!e->slog_phi_valid || e->slog_head <= 0) {
+        e->err = "bh_get_step_log_phi: no step was logged since the log was enabled or the bodies "
+                 "were replaced";
+        return BH_E_STATE;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    SYNC(e, e->stream);
+    const bh_step_record *ring = static_cast<const bh_step_record *>(e->slog_ring);
+    bh_step_record last{};
+    HIPCHK(e, hipMemcpy(&last, ring + (e->slog_head - 1) % e->slog_cap, sizeof(last),
+                        hipMemcpyDeviceToHost));
+    const int64_t n = last.d.n;
+    if (n < 0 || n > e->slog_bcap) {
+        e->err = "bh_get_step_log_phi: the last record's body count is out of range";
+        return BH_E_STATE;
+    }
+    *n_out = n;
+    if (cap < n) return BH_E_CAPACITY;
+    if (n > 0)
+        HIPCHK(e, hipMemcpy(phi, e->slog_stage + 5 * (size_t)e->slog_bcap,
+                            sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
+    return BH_OK;
+}
+
+int bh_step_log_kernel_ms(const bh_engine *e, double *avg_ms, int64_t *launches) {
+    if (!e || !avg_ms) return BH_E_INVALID;
+    if (e->async_running && std::this_thread::get_id() != e->step_thr.get_id()) return BH_E_STATE;
+    *avg_ms = e->slog_launches ? e->slog_ms_sum / (double)e->slog_launches : 0.0;
+    if (launches) *launches = e->slog_launches;
     return BH_OK;
 }
 

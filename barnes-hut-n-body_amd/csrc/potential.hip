@@ -16,6 +16,7 @@
 // The term is a subset of the force term's arithmetic: one sqrt and one reciprocal.  Unlike the
 // force, the own leaf's term m / sqrt(soft2) is not zero, so leaves need the identity test.
 #include "bh_device.hpp"
+#include "diag_sum.hpp"
 #include "fastmath.hpp"
 
 namespace bh {
@@ -160,25 +161,8 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_potential(const Node *__restri
 }
 
 // ---- global diagnostics: fixed-order reductions, no floating-point atomics ----------------
-// Sums over the bodies in the caller's list order (the engine stages the state there first), so
-// the result depends on the list alone, not on the slot order of the last build: thread t of
-// workgroup g adds the bodies g * CHUNK + t, + DIAG_TB, ... in ascending order, the workgroup's
-// threads are combined by a fixed tree in LDS, and one final workgroup adds the partials the
-// same way.  Two calls on the same state therefore return identical bits.
-constexpr int DIAG_TB = 256;
-constexpr int DIAG_K = 8;           // mass, mx, my, px, py, lz, kinetic, sum m * phi
-constexpr int DIAG_MAX_BLOCKS = 1024;
-
-__device__ __forceinline__ void block_tree_sum(double (&v)[DIAG_K], double (*lds)[DIAG_TB]) {
-    for (int k = 0; k < DIAG_K; ++k) lds[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = DIAG_TB / 2; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w)
-            for (int k = 0; k < DIAG_K; ++k) lds[k][threadIdx.x] += lds[k][threadIdx.x + w];
-        __syncthreads();
-    }
-}
-
+// (the partition, the per-thread order and the LDS tree are diag_sum.hpp's, shared with the step
+// log's records)
 __global__ __launch_bounds__(DIAG_TB) void k_diag_partial(int64_t n, int64_t chunk,
                                                           const double *__restrict__ x,
                                                           const double *__restrict__ y,
@@ -188,32 +172,13 @@ __global__ __launch_bounds__(DIAG_TB) void k_diag_partial(int64_t n, int64_t chu
                                                           const double *__restrict__ phi,
                                                           double *__restrict__ part) {
     __shared__ double lds[DIAG_K][DIAG_TB];
-    double v[DIAG_K] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int64_t lo = (int64_t)blockIdx.x * chunk;
-    const int64_t hi = lo + chunk < n ? lo + chunk : n;
-    for (int64_t i = lo + threadIdx.x; i < hi; i += DIAG_TB) {
-        const double xi = x[i], yi = y[i], vxi = vx[i], vyi = vy[i], mi = m[i];
-        v[0] += mi;
-        v[1] += mi * xi;
-        v[2] += mi * yi;
-        v[3] += mi * vxi;
-        v[4] += mi * vyi;
-        v[5] += mi * (xi * vyi - yi * vxi);
-        v[6] += 0.5 * mi * (vxi * vxi + vyi * vyi);
-        if (phi) v[7] += mi * phi[i];
-    }
-    block_tree_sum(v, lds);
-    if (threadIdx.x == 0)
-        for (int k = 0; k < DIAG_K; ++k) part[(size_t)blockIdx.x * DIAG_K + k] = lds[k][0];
+    diag_partial_block((int)blockIdx.x, n, chunk, x, y, vx, vy, m, phi, part, lds);
 }
 
 __global__ __launch_bounds__(DIAG_TB) void k_diag_final(int blocks, const double *__restrict__ part,
                                                         double *__restrict__ out) {
     __shared__ double lds[DIAG_K][DIAG_TB];
-    double v[DIAG_K] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    for (int g = threadIdx.x; g < blocks; g += DIAG_TB)
-        for (int k = 0; k < DIAG_K; ++k) v[k] += part[(size_t)g * DIAG_K + k];
-    block_tree_sum(v, lds);
+    diag_final_block(blocks, part, lds);
     if (threadIdx.x == 0)
         for (int k = 0; k < DIAG_K; ++k) out[k] = lds[k][0];
 }
@@ -240,11 +205,9 @@ size_t diag_partial_doubles() { return (size_t)(DIAG_MAX_BLOCKS + 1) * DIAG_K; }
 
 void diag_reduce(int64_t n, const double *x, const double *y, const double *vx, const double *vy,
                  const double *m, const double *phi, double *part, double *out8, hipStream_t s) {
-    // whole workgroup strides per chunk, at most DIAG_MAX_BLOCKS chunks (n = 0: one, all zeros)
-    int64_t chunk = (n + DIAG_MAX_BLOCKS - 1) / DIAG_MAX_BLOCKS;
-    chunk = (chunk + DIAG_TB - 1) / DIAG_TB * DIAG_TB;
-    if (chunk < DIAG_TB) chunk = DIAG_TB;
-    const int blocks = (int)((n + chunk - 1) / chunk) > 0 ? (int)((n + chunk - 1) / chunk) : 1;
+    const DiagPartition dp = diag_partition(n);
+    const int64_t chunk = dp.chunk;
+    const int blocks = dp.blocks;
     k_diag_partial<<<blocks, DIAG_TB, 0, s>>>(n, chunk, x, y, vx, vy, m, phi, part);
     k_diag_final<<<1, DIAG_TB, 0, s>>>(blocks, part, out8);
 }

@@ -78,12 +78,18 @@ __device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
 // but SALU 10416 -> 15537 (the pop test at every stop, the park test at every internal node) and
 // k_traverse 0.768 -> 0.797 ms (+3.7 %): the wave is issue-bound over both units, so the trade
 // loses.  That walk is in the history at 3db5b68.
-template <bool FAST, bool COUNT, bool OFF32>
+// POT (the step log's kick-only walk, engine.cpp step_log_step): the walk also sums the body's
+// potential over the nodes it takes, s += mass * invR with the block's own invR -- the term and
+// the order of potential.hip's pot_walk, so -(G * s) is bh_compute_potential's phi on this tree.
+// Unlike the force's, the own leaf's term m / sqrt(soft2) is no +-0: it is left out by identity
+// (the exact walk never takes the own leaf; the fast walk does, for its +-0 force).  s is never
+// -0.0 (potential.hip), so a massless node's +-0 term on the fast path leaves it unchanged.
+template <bool FAST, bool COUNT, bool OFF32, bool POT = false>
 __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T, double bx,
                                      double by, double Gm, double soft2, double theta2,
                                      double s2root, double thr0, uint32_t self, uint32_t resume,
                                      double &fx, double &fy, uint32_t &nvis, uint32_t &niters,
-                                     uint32_t &ncontrib, uint32_t &nblocks) {
+                                     uint32_t &ncontrib, uint32_t &nblocks, double &pot) {
     uint32_t cur = 0;
     // one iteration on record `rec`; the next record is requested into `nrec`.  The loop body
     // is unrolled twice with the two records swapping roles (no SGPR copies per iteration).
@@ -168,6 +174,11 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
             const double f = Gm * mass * invR2;
             fx += f * dx * invR;
             fy += f * dy * invR;
+            if (POT) {
+                const bool notself =
+                    !FAST || !((meta & NODE_LEAF) && (meta & NODE_BODY_MASK) == self);
+                pot += notself ? mass * invR : 0.0;
+            }
             resume = next;
         }
         nwait(nrec);
@@ -451,7 +462,8 @@ __device__ __forceinline__ void own_kick(int64_t q, double bx, double by, double
 // it through the leaf records), so the update in place is race-free and a2 is not written.
 // Wave v evaluates the bpw lanes [lo + bpw v, lo + bpw v + bpw) (64 = one body per lane; fewer
 // for small launches, the wave's other lanes idle -- see traverse()): walk, then the epilogue.
-template <bool COUNT, bool OFF32, int KICK, bool BFS>
+// POT: the walk's potential sum (walk<>) goes to phi[slot] as -(G * s); a tombstone gets 0.0.
+template <bool COUNT, bool OFF32, int KICK, bool BFS, bool POT = false>
 __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_start,
                                           const Node *__restrict__ nodes,
                                           const uint32_t *__restrict__ d_T, double *x, double *y,
@@ -462,7 +474,8 @@ __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_s
                                           const KickArgs &kick,
                                           const uint32_t *__restrict__ lanes,
                                           const WaveOrder &wo, uint32_t *lds,
-                                          uint32_t bm_words) {
+                                          uint32_t bm_words, double *__restrict__ phi = nullptr) {
+    static_assert(!POT || (KICK == KICK_ONLY && !COUNT && !BFS), "the step log's walk only");
     const uint32_t lane = threadIdx.x & 63u;
     const bool in_wave = lane < bpw;
     const int64_t q = lo + (int64_t)v * bpw + lane;  // lane
@@ -482,7 +495,7 @@ __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_s
     const double soft2 = fp.soft2, theta2 = fp.theta2;
     const double s2root = g.s2[0];
     const uint32_t self = (uint32_t)p;
-    double fx = 0.0, fy = 0.0;
+    double fx = 0.0, fy = 0.0, pot = 0.0;
     uint32_t nvis = 0, niters = 0, ncontrib = 0, nblocks = 0;
     // lane is active for node `cur` iff cur >= resume; invalid lanes and tombstones never are.
     const uint32_t resume = walks ? 0u : 0xFFFFFFFFu;
@@ -502,11 +515,11 @@ __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_s
     }
     if (walked) {
     } else if (fast)
-        walk<true, COUNT, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, thr0, self, resume,
-                                 fx, fy, nvis, niters, ncontrib, nblocks);
+        walk<true, COUNT, OFF32, POT>(nodes, T, bx, by, Gm, soft2, theta2, s2root, thr0, self,
+                                      resume, fx, fy, nvis, niters, ncontrib, nblocks, pot);
     else
-        walk<false, COUNT, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, thr0, self, resume,
-                                  fx, fy, nvis, niters, ncontrib, nblocks);
+        walk<false, COUNT, OFF32, POT>(nodes, T, bx, by, Gm, soft2, theta2, s2root, thr0, self,
+                                       resume, fx, fy, nvis, niters, ncontrib, nblocks, pot);
     if (wo.cost && lane == 0 && q < hi)
         wo.cost[v] = (uint32_t)(wall_clock64() - t_start < 0xFFFFFFull
                                     ? wall_clock64() - t_start : 0xFFFFFFull);
@@ -534,6 +547,7 @@ __device__ __forceinline__ void trav_wave(uint32_t v, uint32_t bpw, uint64_t t_s
         return;
     }
     if (!valid) return;
+    if (POT) phi[p] = walks ? -(fp.G * pot) : 0.0;
     // BHA:390-391, interleaved (ax, ay): coalesced 16-byte stores in Morton order
     typedef double double2_t __attribute__((ext_vector_type(2)));
     double2_t acc;
@@ -610,6 +624,33 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_traverse(const Node *__restric
         v = wo.order[v / BH_TRAV_XCD_RUN] * BH_TRAV_XCD_RUN + v % BH_TRAV_XCD_RUN;
     trav_wave<COUNT, OFF32, KICK, BFS>(v, bpw, t_start, nodes, d_T, x, y, m, cidx, lo, hi, fp, g,
                                        a2, cnt, kick, lanes, wo, trav_lds, bm_words);
+}
+
+// The step log's entry: k_traverse<false, OFF32, KICK_ONLY, false> with the potential (POT), a
+// kernel of its own so that k_traverse's signature and instantiations stay what they are.
+template <bool OFF32>
+__global__ __launch_bounds__(TB * MAX_WPB) void k_traverse_pot(
+    const Node *__restrict__ nodes, const uint32_t *__restrict__ d_T, double *x, double *y,
+    const double *__restrict__ m, const uint32_t *__restrict__ cidx, int64_t lo, int64_t hi,
+    ForceParams fp, Geometry g, double *__restrict__ a2, KickArgs kick,
+    const uint32_t *__restrict__ lanes, WaveOrder wo, uint32_t bpw, uint32_t wpb,
+    double *__restrict__ phi) {
+#if defined(BH_TRAV_TIMING)
+    const uint64_t t_start = wall_clock64();
+#else
+    const uint64_t t_start = wo.cost ? wall_clock64() : 0;
+#endif
+    uint32_t b = blockIdx.x;  // (k_traverse's remap)
+    {
+        const uint32_t C = BH_TRAV_XCD_RUN / wpb, G = xcd_group_blocks(wpb);
+        const uint32_t full = xcd_full_groups(gridDim.x, wpb);
+        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
+    }
+    uint32_t v = b * wpb + (threadIdx.x >> 6);
+    if (wo.order) v = wo.order[v / BH_TRAV_XCD_RUN] * BH_TRAV_XCD_RUN + v % BH_TRAV_XCD_RUN;
+    trav_wave<false, OFF32, KICK_ONLY, false, true>(
+        v, bpw, t_start, nodes, d_T, x, y, m, cidx, lo, hi, fp, g, a2,
+        TraverseCounters{nullptr, nullptr, nullptr, nullptr}, kick, lanes, wo, nullptr, 0u, phi);
 }
 
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {  // splitmix64 finaliser
@@ -827,7 +868,9 @@ static int64_t bfs_max_bodies(int kick_mode) {
 
 // (one-GPU evaluations of the whole list only: a rank's lane range walks a tree of every rank's
 // bodies, which the bitmap's size estimate does not cover)
-bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting) {
+bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
+                     bool pot) {
+    if (pot) return false;  // (the step log's walk is the cursor walk: bfs_walk has no potential)
     const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
     return !counting && off32 && lo == 0 && hi > 0 && hi <= bfs_max_bodies(kick_mode) &&
            kick_mode != KICK_OWN_DRIFT && kick_mode != KICK_OWN_ONLY;
@@ -836,10 +879,10 @@ bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, boo
 // The launch shape of traverse() over [lo, hi): the one place that picks it (bh_launch_plan reads
 // it out through the same call).
 TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
-                             bool ordered) {
+                             bool ordered, bool pot) {
     TraverseShape t{};
     if (hi <= lo) return t;
-    t.bfs = traverse_is_bfs(node_cap, lo, hi, kick_mode, counting);
+    t.bfs = traverse_is_bfs(node_cap, lo, hi, kick_mode, counting, pot);
     if (t.bfs) {
         // (a one-GPU tree has ~1.7 nodes per body: C1 21 565 for 12 500, 3 511 for 2 000)
         const size_t bits = std::min<size_t>(node_cap, (size_t)(9 * (hi - lo) / 4 + 256));
@@ -860,12 +903,13 @@ TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_m
 void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x, double *y,
               const double *m, const uint32_t *cidx, int64_t lo, int64_t hi, const Geometry &g,
               const ForceParams &fp, double *a2, const TraverseCounters *cnt,
-              hipStream_t s, const KickArgs *kick, const uint32_t *lanes, const WaveOrder *wo) {
+              hipStream_t s, const KickArgs *kick, const uint32_t *lanes, const WaveOrder *wo,
+              double *phi) {
     if (hi <= lo) return;
     // node records addressed by a 32-bit byte offset while the array stays below 4 GiB
     const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
     const TraverseShape t = traverse_shape(node_cap, lo, hi, kick ? kick->mode : KICK_NONE,
-                                           cnt != nullptr, wo && wo->order);
+                                           cnt != nullptr, wo && wo->order, phi != nullptr);
     const bool bfs = t.bfs;
     const uint32_t bm_words = t.bm_words, bpw = t.bpw, wpb = t.wpb;
     const unsigned grid = t.groups;  // workgroups
@@ -873,6 +917,15 @@ void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x
     const size_t lds = bfs ? bfs_lds_bytes(bm_words) : 0;
     const KickArgs ka = kick ? *kick : KickArgs{KICK_NONE, nullptr, nullptr, 0.0, 0.0, nullptr};
     const TraverseCounters tc = cnt ? *cnt : TraverseCounters{nullptr, nullptr, nullptr, nullptr};
+    if (phi) {  // the step log's kick-only walk (engine.cpp checks the mode before it asks)
+        if (off32)
+            k_traverse_pot<true><<<grid, TB * wpb, 0, s>>>(nodes, d_T, x, y, m, cidx, lo, hi, fp, g,
+                                                           a2, ka, lanes, w, bpw, wpb, phi);
+        else
+            k_traverse_pot<false><<<grid, TB * wpb, 0, s>>>(nodes, d_T, x, y, m, cidx, lo, hi, fp,
+                                                            g, a2, ka, lanes, w, bpw, wpb, phi);
+        return;
+    }
 #define BH_TRAV(C, O, K, B)                                                                  \
     k_traverse<C, O, K, B><<<grid, TB * wpb, lds, s>>>(nodes, d_T, x, y, m, cidx, lo, hi, fp, g, \
                                                        a2, tc, ka, lanes, w, bpw, wpb, bm_words)

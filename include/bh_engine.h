@@ -202,7 +202,8 @@ int bh_step(bh_engine *e, int32_t k);
  * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
  * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
- * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers.
+ * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers, and
+ * bh_set_step_log, bh_get_step_log and bh_get_step_log_phi.
  * bh_step_positions blocks until the call's positions and masses are final -- on one GPU that is
  * once its last merge rule is done, before its last traversal; else when the call ends -- and
  * returns the mirror planes x, y, m of the list after the call (n_out bodies; the other buffer
@@ -557,6 +558,65 @@ int bh_tracer_launch_shape(int64_t n_tracer, int64_t *out3);
  * no build, no state change, BH_E_STATE between bh_step_begin and bh_step_end.  n_tracer = 0:
  * owner all 0xFFFFFFFF, counts all 0. */
 int bh_render_tracers(bh_engine *e, const bh_view *v, uint32_t *owner, uint32_t *counts);
+
+/* The step log: the conservation read-out of every step, made inside bh_step -- the energy-drift
+ * curve of a run from inside the pipelined k-step call, without one-step calls and without a
+ * separate potential walk per step.  While the log is on, every PhysicsEngine.step() that bh_step
+ * runs appends one record to a ring on the device; nothing waits for the host and nothing is
+ * copied per step; bh_get_step_log reads the ring out in one copy.
+ * One record describes the state after the step's second kick (BHA:432) and before its merge rule
+ * (BHA:438) -- positions and velocities both at t + dt, the only instant of a step at which kinetic
+ * and potential energy belong together -- in its own terms, because a re-build would jitter again:
+ *   root   the tree of the step's second evaluation (BHA:426), after that build's jitter;
+ *   L      the reference's body list at BHA:432: bodies removed by earlier steps -- earlier steps
+ *          of the same call included -- are gone, the order is what removeAt leaves;
+ *   phi_b  for every body b of L exactly what bh_compute_potential defines over root:
+ *          accumulateForce's nodes, mass-0 nodes skipped, the own leaf skipped by identity, an
+ *          internal node taken iff s2 < theta^2 * dist2 (strict), the terms mass * (1.0 / sqrt(r2))
+ *          in IEEE arithmetic added in pre-order from +0.0, phi_b = -(G * s); a body outside the
+ *          root cell walks.  The sum rides in the step's own second traversal (the force's point
+ *          blocks hold 1 / sqrt(r2) already); at theta = 0 it is the all-pairs kernel's;
+ *   d      what bh_compute_diagnostics' reduction returns for the six planes x, y, vx, vy, m, phi
+ *          of L in list order: the same partition by |L|, the same fixed trees, no floating-point
+ *          atomics; d.n = |L|, d.potential = 0.5 * sum m phi.
+ * So a step that neither jitters nor merges logs, bit for bit, what bh_compute_diagnostics(e', 1, .)
+ * returns after the same step on a twin engine.  The records do not depend on how steps are
+ * grouped into calls (k steps in one call = k one-step calls, removals included), on the lane map,
+ * the mirror, tracers or profiling, and the log changes nothing else: bodies, tracers, removals
+ * and every other output of bh_step are bit for bit what they are with the log off.
+ *
+ * bh_set_step_log: capacity 0 turns the log off and frees its buffers; 1..1<<20 makes a ring of
+ * that many records, empty, with step and t back at 0.  The ring overwrites its oldest record.
+ * The log persists across bh_reset_bodies, bh_set_params and bh_load_state, step and t running on
+ * (dt is read per call, as bh_step reads it); it is not written by bh_save_state.  bh_step(e, 0)
+ * logs nothing; with N = 0 a step logs an all-zero d, step and t advancing.  A call replayed for
+ * a merge mailbox overflow logs each step once; a bh_step that returns an error empties the ring
+ * and puts step and t back to their values before the call.  Steps of a bh_step_begin call are
+ * logged like any others; until bh_step_end the two getters and bh_set_step_log return BH_E_STATE.
+ * BH_E_INVALID: e NULL, capacity outside 0..1<<20.  BH_E_STATE with capacity > 0 on any engine
+ * that is not the one-GPU engine -- bh_create_dist, bh_create_local and bh_create_solo engines and
+ * a multi-device handle with more than one member: a locally essential tree is no full tree, and
+ * no walk of one gives a body its full potential (bh_last_error says so); 0 is accepted everywhere.
+ * bh_get_step_log: the ring oldest first, *n_out = min(records logged, capacity) of them;
+ * BH_E_CAPACITY + *n_out if cap is too small.  bh_get_step_log_phi: the phi plane of the newest
+ * record in the order of its L, d.n entries; BH_E_CAPACITY + *n_out likewise; BH_E_STATE if no step
+ * was logged since the log was enabled or since the last bh_reset_bodies / bh_load_state; with the
+ * log off, *n_out = 0.  Both: BH_E_INVALID for e or n_out NULL, or the array NULL with cap > 0. */
+typedef struct bh_step_record {
+    int64_t step;        /* 1, 2, ...: steps logged since bh_set_step_log enabled the log */
+    double t;            /* sum of those steps' dt, added in binary64 in step order from +0.0 */
+    bh_diagnostics d;    /* the state after the step's second kick, before its merge rule */
+} bh_step_record;
+int bh_set_step_log(bh_engine *e, int64_t capacity);
+int bh_get_step_log(bh_engine *e, bh_step_record *out, int64_t cap, int64_t *n_out);
+int bh_get_step_log_phi(bh_engine *e, double *phi, int64_t cap, int64_t *n_out);
+
+/* Average HIP-event duration (ms) of the log's own kernels per step of the last bh_step call --
+ * the staging into list order and the reduction, not the walk, which bh_traverse_kernel_ms times --
+ * and their number (one per step), as bh_tracer_kernel_ms reports the tracer walks: taken only
+ * while bh_set_profiling(e, 1), otherwise *launches = 0; counted under phase [2] of
+ * bh_last_timings. */
+int bh_step_log_kernel_ms(const bh_engine *e, double *avg_ms, int64_t *launches);
 
 /* Indices (into the list as it was before the last bh_step call, ascending) of the bodies the
  * merge rule removed during that call — what a shim needs to apply BHA:519's removeAt to the
