@@ -51,6 +51,7 @@ EXPORTED_SYMBOLS = (
     "bh_nbody3d_center_of_mass", "bh_default_view", "bh_render_bodies", "bh_render_kernel_ms",
     "bh_launch_plan", "bh_render_quads", "bh_render_quads_kernel_ms",
     "bh_compute_field", "bh_field_kernel_ms",
+    "bh_find_neighbors", "bh_neighbors_kernel_ms", "bh_neighbor_reach",
     "bh_compute_field_direct", "bh_compute_force_error", "bh_direct_field_kernel_ms",
     "bh_direct_field_shape",
     "bh_compute_field_grid", "bh_field_grid_of_view", "bh_field_grid_kernel_ms",
@@ -276,6 +277,10 @@ def load_library(path: str | None = None):
     lib.bh_potential_kernel_ms.argtypes = [_VP, _D]
     lib.bh_compute_field.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
     lib.bh_field_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_find_neighbors.argtypes = [_VP, ctypes.c_int64, _D, _D, ctypes.c_double, _D, _I64P,
+                                      _I64P, _D, _I64P, _I64P, ctypes.c_int64, _I64P]
+    lib.bh_neighbors_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_neighbor_reach.argtypes = [ctypes.POINTER(BhParams), ctypes.c_int32, _D]
     lib.bh_compute_field_direct.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
     lib.bh_compute_force_error.argtypes = [_VP, ctypes.c_int64, _I64P, _D, _D, _D, _D,
                                            ctypes.POINTER(BhForceError)]
@@ -446,6 +451,18 @@ def tracer_launch_shape(n: int):
     if rc != BH_OK:
         raise BhError(rc, "bh_tracer_launch_shape: invalid arguments")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def neighbor_reach(depth: int, params: BhParams | None = None) -> float:
+    """The pruning bound of find_neighbors' walk at tree depth `depth` for the root cell of
+    `params` (bh_neighbor_reach; host-only, no device): every findable body under a depth-`depth`
+    internal node lies within this distance of the node's centre of mass."""
+    p = params if params is not None else default_params()
+    out = ctypes.c_double(0.0)
+    rc = load_library().bh_neighbor_reach(ctypes.byref(p), int(depth), ctypes.byref(out))
+    if rc != BH_OK:
+        raise BhError(rc, "bh_neighbor_reach: invalid arguments")
+    return out.value
 
 
 def field_grid_shape(nx: int, ny: int):
@@ -817,6 +834,56 @@ class Engine:
     def field_kernel_ms(self) -> float:
         """HIP-event time (ms) of the last field kernel launch (bh_field_kernel_ms)."""
         return self._kernel_ms(self._lib.bh_field_kernel_ms)
+
+    def find_neighbors(self, px, py, r, lists=False, counts=True, cap=None):
+        """bh_find_neighbors: the bodies within r of the probe points (px, py); r is one radius
+        or an array of one per probe.  Returns (count, nearest, d2_nearest) per probe -- nearest
+        is an index into get_bodies() after the call, smallest under (d2, index), -1 and +inf if
+        there is none -- and with lists=True also (offsets, indices): probe j's neighbours are
+        indices[offsets[j]:offsets[j + 1]], ascending.  Found iff dx*dx + dy*dy <= r*r among the
+        bodies in the tree of non-zero mass; a probe on a body finds it.  counts=False (without
+        lists): count is None, and the walk may shrink each probe's radius to the best distance
+        so far -- the same nearest, the call for picking one body.  A build, exactly as
+        compute_field (the jitter may move positions); the probes never enter the state.  A
+        list capacity (cap; None: a guess) that is too small costs one re-call."""
+        px = np.ascontiguousarray(px, dtype=np.float64)
+        py = np.ascontiguousarray(py, dtype=np.float64)
+        n = len(px)
+        if px.ndim != 1 or py.shape != px.shape:
+            raise ValueError("px and py must be 1-d arrays of equal length")
+        pr = None
+        if np.ndim(r) != 0:
+            pr = np.ascontiguousarray(r, dtype=np.float64)
+            if pr.shape != px.shape:
+                raise ValueError("r must be a scalar or have the length of px")
+        r0 = 0.0 if pr is not None else float(r)
+        count = np.empty(n, dtype=np.int64) if counts or lists else None
+        nearest = np.empty(n, dtype=np.int64)
+        d2 = np.empty(n, dtype=np.float64)
+        i64 = lambda a: a.ctypes.data_as(_I64P) if a is not None else None  # noqa: E731
+        if not lists:
+            self._check(self._lib.bh_find_neighbors(self._h, n, _dp(px), _dp(py), r0, _dp(pr),
+                                                    i64(count), i64(nearest), _dp(d2), None,
+                                                    None, 0, None))
+            return count, nearest, d2
+        offsets = np.empty(n + 1, dtype=np.int64)
+        total = ctypes.c_int64(0)
+        cap = max(64, 8 * n) if cap is None else int(cap)
+        for _ in range(2):
+            indices = np.empty(max(cap, 1), dtype=np.int64)
+            rc = self._lib.bh_find_neighbors(self._h, n, _dp(px), _dp(py), r0, _dp(pr),
+                                             i64(count), i64(nearest), _dp(d2), i64(offsets),
+                                             i64(indices), cap, ctypes.byref(total))
+            if rc != BH_E_CAPACITY:
+                break
+            cap = total.value
+        self._check(rc)
+        return count, nearest, d2, offsets, indices[:total.value].copy()
+
+    def neighbors_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last find_neighbors call's device work, first walk to
+        last kernel (bh_neighbors_kernel_ms)."""
+        return self._kernel_ms(self._lib.bh_neighbors_kernel_ms)
 
     def compute_field_direct(self, px, py, pm=None, want_accel=True, want_phi=True):
         """bh_compute_field_direct: compute_field with no cell ever accepted, whatever the
@@ -1320,6 +1387,18 @@ class PhysicsEngine:
         got = self._eng.render_quads(view_x, view_y, zoom, width, height)
         self._pull()
         return got
+
+    def pick(self, x, y, r):
+        """The Body of the caller's list nearest to (x, y) within r -- the body under the cursor
+        -- or None (Engine.find_neighbors: among the bodies in the tree of non-zero mass, ties to
+        the lower list index).  Builds a tree as step()'s first half does, so its jitter is
+        written back into the Body objects."""
+        self._eng.set_params(self._params())
+        if self._changed():
+            self._push()
+        _, nearest, _ = self._eng.find_neighbors([float(x)], [float(y)], float(r), counts=False)
+        self._pull()
+        return self._bodies[int(nearest[0])] if nearest[0] >= 0 else None
 
     getBodies = get_bodies
     resetBodies = reset_bodies

@@ -760,6 +760,54 @@ size_t field_grid_stat_partials();
 void field_grid_stats(int64_t n, const double *ax, const double *ay, const double *phi,
                       bh_field_grid_stats *part, bh_field_grid_stats *out, hipStream_t s);
 
+// ---- launchers (neighbors.hip): bodies within a radius of probe points ------------------
+// The pruning bound of the radius walk (bh_find_neighbors).  Every leaf under an
+// internal node of depth d whose mass passes mass_ok() lies within neighbor_reach_at(rc, d) of the
+// node's (comX, comY); a node whose mass does not pass is always opened.  Made on the host by
+// neighbor_reach_terms for the engine's root cell; the kernel evaluates neighbor_reach_at itself
+// (an exact scaling and one addition: the same bits on host and device), and bh_neighbor_reach
+// reports it.
+struct NeighborReach {
+    double diag0;   // the root cell's diagonal 2 sqrt(2) h_0, with the relative margin
+    double slack;   // what does not shrink with depth: jitter allowance + COM rounding, with margin
+    uint32_t m_lo;  // high word of the smallest node mass the COM's error bound covers (2^-900)
+    uint32_t m_span;  // ... of the first one beyond it, minus m_lo
+};
+NeighborReach neighbor_reach_terms(const Geometry &g);
+__host__ __device__ inline double neighbor_reach_at(const NeighborReach &rc, int depth) {
+    return __builtin_ldexp(rc.diag0, -depth) + rc.slack;
+}
+// r * NEIGHBOR_RADIUS_PAD is the radius the pruning compare uses: (r pad + reach)^2 evaluated in
+// binary64 then stays above the exact (r + reach)^2 with every rounding of both sides counted
+constexpr double NEIGHBOR_RADIUS_PAD = 1.0 + 0x1p-40;
+// The candidate set is the leaf sequence of leaf_list_build: every non-empty leaf under no mass-0
+// node.  Probe j = (px[j], py[j]) with radius pr[j] (pr null: r) finds leaf body b iff
+// rj >= 0 && dx*dx + dy*dy <= rj*rj, dx = x_b - px[j], dy = y_b - py[j] (binary64, nothing fused);
+// a probe with a NaN coordinate or a NaN or negative radius finds nothing.  Lane q walks probe
+// order[q]; the launch shape is field_walk's.  d_T null: no tree (nodes and cidx are not read).
+// neighbors_count: count[j] = the number found (count has n + 1 entries; the last is set to 0 for
+// the scan) and, with nearest / d2n non-null (both or neither), the caller index cidx[slot] of
+// the smallest under (d2, caller index) and its d2, or -1 and +inf.
+void neighbors_count(const Node *nodes, size_t node_cap, const uint32_t *d_T, const uint32_t *cidx,
+                     const double *px, const double *py, const double *pr, double r,
+                     const uint32_t *order, int64_t n, const NeighborReach &rc, int64_t *count,
+                     int64_t *nearest, double *d2n, hipStream_t s);
+// offsets[0 .. n] = exclusive scan of count[0 .. n]; scratch: neighbors_scan_bytes(n)
+size_t neighbors_scan_bytes(int64_t n);
+hipError_t neighbors_offsets(int64_t n, const int64_t *count, int64_t *offsets, void *scratch,
+                             size_t scratch_bytes, hipStream_t s);
+// The same walk again: probe j's caller indices into idx[offsets[j] .. offsets[j + 1]), in
+// pre-order (never past its segment's end).
+void neighbors_fill(const Node *nodes, size_t node_cap, const uint32_t *d_T, const uint32_t *cidx,
+                    const double *px, const double *py, const double *pr, double r,
+                    const uint32_t *order, int64_t n, const NeighborReach &rc,
+                    const int64_t *offsets, uint32_t *idx, hipStream_t s);
+// Every segment of idx (total entries < 2^31, keys below 2^bits) ascending into out, as int64.
+// idx_s: total entries of scratch; *scratch_bytes = 0: only the size needed is returned in it.
+hipError_t neighbors_sort(int64_t total, int64_t n, const int64_t *offsets, uint32_t *idx,
+                          uint32_t *idx_s, int bits, int64_t *out, void *scratch,
+                          size_t &scratch_bytes, hipStream_t s);
+
 // ---- launchers (render.hip) ------------------------------------------------------
 // The body pass of a frame (PNL:302-307).  Working planes `packed` and `cnt` (null: no density):
 // render_padded_pixels() uint32 each, zero on entry to render_raster and zero again after

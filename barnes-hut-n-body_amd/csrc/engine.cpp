@@ -261,6 +261,21 @@ struct bh_engine {
     int64_t fgr_cap = 0;
     Stopwatch fgr_sw;  // around the last k_field_grid launch
 
+    // bh_find_neighbors (neighbors.hip): the call's own buffers, allocated on first use and grown
+    // when needed -- per probe (nbr_cap) and per list entry (nbr_list_cap)
+    double *nbr_in = nullptr;      // px, py, pr planes of nbr_cap probes
+    uint32_t *nbr_u32 = nullptr;   // key, sorted key, index, order planes
+    int64_t *nbr_i64 = nullptr;    // count, offsets (nbr_cap + 1 each), nearest
+    double *nbr_d2 = nullptr;      // d2_nearest
+    void *nbr_scratch = nullptr;   // the probes' sort and the counts' scan
+    size_t nbr_scratch_bytes = 0;
+    int64_t nbr_cap = 0;
+    uint32_t *nbr_idx = nullptr;   // the lists as written and as sorted, nbr_list_cap each
+    int64_t *nbr_list = nullptr;   // ... and as int64, for the copy-out
+    int64_t nbr_list_cap = 0;
+    void *nbr_sort = nullptr;      // the segmented sort's scratch
+    size_t nbr_sort_bytes = 0;
+    Stopwatch nbr_sw;  // from the first walk to the last kernel of the last call
     // bh_set_tracers (field.hip k_tracer_step): the tracer list and its lane map.  Nothing is
     // allocated while the list is empty; every buffer is sized for exactly trc_n tracers and made
     // anew when the count changes (a stale lane map would index past the planes)
@@ -1833,6 +1848,106 @@ int field_grid_launch(bh_engine *e, const bh_field_grid &g, unsigned planes, boo
         HIPCHK(e, hipGetLastError());
     }
     return BH_OK;
+}
+
+// The caller's arguments of bh_find_neighbors (host arrays; pr nullable), what it asked for, and
+// what the launch found out.
+struct NeighborQuery {
+    int64_t n;
+    const double *px, *py, *pr;
+    double r;
+    bool counting;  // counts (and with them offsets and the total) are wanted
+    bool nearest;   // nearest / d2_nearest are wanted
+    bool lists;     // offsets and indices are wanted, `cap` entries of room
+    int64_t cap;
+    int64_t total = 0;    // neighbours in all (counting)
+    bool filled = false;  // the lists were written: total <= cap
+};
+
+// The planes of e->nbr_i64: count and offsets of nbr_cap + 1 entries each, then nearest.
+struct NeighborPlanes {
+    int64_t *count, *offsets, *nearest;
+};
+NeighborPlanes neighbor_planes(const bh_engine *e) {
+    const size_t cap1 = (size_t)e->nbr_cap + 1;
+    return NeighborPlanes{e->nbr_i64, e->nbr_i64 + cap1, e->nbr_i64 + 2 * cap1};
+}
+
+// bh_find_neighbors: upload, key and sort the probes as bh_compute_field does, then the radius
+// walk for counts and nearest, the scan of the counts and -- if lists are asked for and fit -- the
+// second walk and the segmented sort, all into the engine's own planes.  The stopwatch runs from
+// the first walk to the last kernel; with lists it spans the read-back of the total in between.
+int neighbors_launch(bh_engine *e, NeighborQuery &q, bool tree) {
+    const int64_t P = q.n;
+    if (outgrown(e->nbr_cap, e->nbr_in, P)) {
+        const size_t cap = (size_t)P;
+        TRY(dev_alloc(e, e->nbr_in, 3 * cap));       // px, py, pr
+        TRY(dev_alloc(e, e->nbr_u32, 4 * cap));      // key, sorted key, index, order
+        TRY(dev_alloc(e, e->nbr_i64, 3 * cap + 2));  // count, offsets, nearest
+        TRY(dev_alloc(e, e->nbr_d2, cap));
+        if (e->nbr_scratch) (void)hipFree(e->nbr_scratch);
+        e->nbr_scratch = nullptr;
+        e->nbr_scratch_bytes = std::max(field_sort_bytes(P), neighbors_scan_bytes(P));
+        HIPCHK(e, hipMalloc(&e->nbr_scratch, e->nbr_scratch_bytes ? e->nbr_scratch_bytes : 1));
+        e->nbr_cap = P;
+    }
+    const size_t cap = (size_t)e->nbr_cap;
+    double *px = e->nbr_in, *py = px + cap, *pr = q.pr ? py + cap : nullptr;
+    TRY(upload_probes(e, Probes{P, q.px, q.py, q.pr}, px, py, pr));
+    uint32_t *key = e->nbr_u32, *key_s = key + cap, *idx = key_s + cap, *order = idx + cap;
+    HIPCHK(e, field_order(P, px, py, e->geo, key, key_s, idx, order, e->nbr_scratch,
+                          e->nbr_scratch_bytes, e->stream));
+    const NeighborPlanes pl = neighbor_planes(e);
+    const Node *nodes = tree ? e->nodes : nullptr;
+    const size_t node_cap = tree ? e->node_cap : 0;
+    const uint32_t *d_T = tree ? e->base + e->n : nullptr;
+    const uint32_t *cidx = tree ? e->st.cidx : nullptr;
+    const NeighborReach rc = neighbor_reach_terms(e->geo);
+    if (q.counting) HIPCHK(e, hipMemsetAsync(pl.count + P, 0, sizeof(int64_t), e->stream));
+    TRY(e->nbr_sw.start(e, e->stream));
+    neighbors_count(nodes, node_cap, d_T, cidx, px, py, pr, q.r, order, P, rc,
+                    q.counting ? pl.count : nullptr, q.nearest ? pl.nearest : nullptr, e->nbr_d2,
+                    e->stream);
+    HIPCHK(e, hipGetLastError());
+    if (q.counting) {
+        HIPCHK(e, neighbors_offsets(P, pl.count, pl.offsets, e->nbr_scratch, e->nbr_scratch_bytes,
+                                    e->stream));
+        HIPCHK(e, hipMemcpyAsync(&q.total, pl.offsets + P, sizeof(int64_t), hipMemcpyDeviceToHost,
+                                 e->stream));
+        SYNC(e, e->stream);
+    }
+    if (q.lists && q.total <= q.cap && q.total > 0) {
+        if (q.total > (int64_t)INT32_MAX) {
+            e->err = "bh_find_neighbors: more than 2^31 - 1 neighbours in all: ask in batches";
+            return BH_E_INVALID;
+        }
+        if (outgrown(e->nbr_list_cap, e->nbr_idx, q.total)) {
+            TRY(dev_alloc(e, e->nbr_idx, 2 * (size_t)q.total));
+            TRY(dev_alloc(e, e->nbr_list, (size_t)q.total));
+            e->nbr_list_cap = q.total;
+        }
+        uint32_t *raw = e->nbr_idx, *sorted = raw + e->nbr_list_cap;
+        neighbors_fill(nodes, node_cap, d_T, cidx, px, py, pr, q.r, order, P, rc, pl.offsets, raw,
+                       e->stream);
+        HIPCHK(e, hipGetLastError());
+        int bits = 1;  // caller indices are below the list's size
+        while (((int64_t)1 << bits) < e->n) ++bits;
+        size_t need = 0;
+        HIPCHK(e, neighbors_sort(q.total, P, pl.offsets, raw, sorted, bits, e->nbr_list, nullptr,
+                                 need, e->stream));
+        if (need > e->nbr_sort_bytes || !e->nbr_sort) {
+            if (e->nbr_sort) (void)hipFree(e->nbr_sort);
+            e->nbr_sort = nullptr;
+            e->nbr_sort_bytes = 0;
+            HIPCHK(e, hipMalloc(&e->nbr_sort, need));
+            e->nbr_sort_bytes = need;
+        }
+        size_t have = e->nbr_sort_bytes;
+        HIPCHK(e, neighbors_sort(q.total, P, pl.offsets, raw, sorted, bits, e->nbr_list,
+                                 e->nbr_sort, have, e->stream));
+    }
+    q.filled = q.lists && q.total <= q.cap;
+    return e->nbr_sw.stop(e, e->stream);
 }
 
 int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fused = nullptr,
@@ -3545,11 +3660,14 @@ void bh_destroy(bh_engine *e) {
                     e->rnd_pixels, e->rnd_owner, e->rnd_counts, e->qd_rowd, e->qd_cold, e->qd_dir,
                     e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch,
                     e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats,
+                    e->nbr_in, e->nbr_u32, e->nbr_i64, e->nbr_d2, e->nbr_scratch, e->nbr_idx,
+                    e->nbr_list, e->nbr_sort,
                     e->trc, e->trc_snap, e->trc_u32, e->trc_scratch, e->slog_ring, e->slog_phi,
                     e->slog_stage, e->slog_part, e->slog_keep, e->slog_pos, e->slog_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
-    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->rnd_sw, &e->qd_sw})
+    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->nbr_sw, &e->rnd_sw,
+                          &e->qd_sw})
         sw->destroy();
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
@@ -4230,6 +4348,61 @@ int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const doub
 
 int bh_field_kernel_ms(const bh_engine *e, double *ms) {
     return kernel_ms(e, &bh_engine::fld_sw, ms);
+}
+
+int bh_find_neighbors(bh_engine *e, int64_t n_probe, const double *px, const double *py, double r,
+                      const double *pr, int64_t *count, int64_t *nearest, double *d2_nearest,
+                      int64_t *offsets, int64_t *indices, int64_t cap, int64_t *n_total) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    TRY(check_list(e, "bh_find_neighbors", "n_probe", n_probe, px && py, "px or py"));
+    const char *bad = nullptr;
+    if (!pr && !(r >= 0.0)) bad = "r must be >= 0";
+    else if ((offsets != nullptr) != (indices != nullptr)) bad = "offsets or indices is NULL";
+    else if (cap < 0) bad = "cap must be >= 0";
+    if (bad) {
+        e->err = std::string("bh_find_neighbors: ") + bad;
+        return BH_E_INVALID;
+    }
+    NeighborQuery q{n_probe, px, py, pr, r, false, nearest || d2_nearest, offsets != nullptr, cap};
+    q.counting = count || q.lists || n_total || !q.nearest;
+    TRY(query_call(e, [&](bh_engine *m, bool run) {
+        if (q.n == 0) run = false;
+        TRY(field_rank(m, run, [&](bool tree) { return neighbors_launch(m, q, tree); }));
+        if (!run) return BH_OK;
+        const NeighborPlanes pl = neighbor_planes(m);
+        const size_t P = (size_t)q.n;
+        auto out = [&](void *dst, const void *src, size_t bytes) {
+            if (dst && bytes) HIPCHK(m, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            return BH_OK;
+        };
+        TRY(out(count, pl.count, sizeof(int64_t) * P));
+        TRY(out(nearest, pl.nearest, sizeof(int64_t) * P));
+        TRY(out(d2_nearest, m->nbr_d2, sizeof(double) * P));
+        TRY(out(offsets, pl.offsets, sizeof(int64_t) * (P + 1)));
+        if (q.filled) TRY(out(indices, m->nbr_list, sizeof(int64_t) * (size_t)q.total));
+        return BH_OK;
+    }));
+    if (q.n == 0 && offsets) offsets[0] = 0;
+    if (n_total) *n_total = q.total;
+    if (q.lists && !q.filled && q.n > 0) {
+        e->err = "bh_find_neighbors: cap is below the total; *n_total and offsets hold it";
+        return BH_E_CAPACITY;
+    }
+    return BH_OK;
+}
+
+int bh_neighbors_kernel_ms(const bh_engine *e, double *ms) {
+    return kernel_ms(e, &bh_engine::nbr_sw, ms);
+}
+
+int bh_neighbor_reach(const bh_params *p, int32_t depth, double *reach) {
+    if (!p || !reach || depth < 0 || depth >= MAX_DEPTH_TAB) return BH_E_INVALID;
+    Geometry g;
+    std::string err;
+    if (make_geometry(*p, g, err) != BH_OK) return BH_E_INVALID;
+    *reach = neighbor_reach_at(neighbor_reach_terms(g), depth);
+    return BH_OK;
 }
 
 int bh_compute_field_direct(bh_engine *e, int64_t n_probe, const double *px, const double *py,

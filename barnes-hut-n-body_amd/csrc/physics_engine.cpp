@@ -289,6 +289,18 @@ bh_force_error PhysicsEngine::forceError(const std::vector<int64_t> &idx,
     return fe;
 }
 
+Body *PhysicsEngine::pick(double x, double y, double r) {
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    int64_t nearest = -1;
+    double d2 = 0.0;
+    // (nearest alone: the walk shrinks the radius to the best distance so far)
+    check(bh_find_neighbors(eng_, 1, &x, &y, r, nullptr, nullptr, &nearest, &d2, nullptr, nullptr,
+                            0, nullptr));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+    return nearest >= 0 ? &(*bodies_)[(size_t)nearest] : nullptr;
+}
+
 void PhysicsEngine::setTracers(const std::vector<double> &x, const std::vector<double> &y,
                                const std::vector<double> &vx, const std::vector<double> &vy) {
     const size_t n = x.size();

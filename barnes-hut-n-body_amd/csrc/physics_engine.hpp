@@ -107,6 +107,13 @@ public:
                               std::vector<double> &ayTree, std::vector<double> &axExact,
                               std::vector<double> &ayExact);
 
+    // The body of the caller's list nearest to (x, y) within r -- the body under the cursor
+    // (PNL:133-178 adds bodies by mouse) -- or nullptr (bh_find_neighbors with one probe; no
+    // reference counterpart): among the bodies in the tree of non-zero mass, found iff
+    // dx*dx + dy*dy <= r*r, ties to the lower list index.  Builds a tree as step()'s first half
+    // does -- its jitter is written back into the list; the pointer is into that list.
+    Body *pick(double x, double y, double r);
+
     // Tracers (bh_set_tracers; no reference counterpart): massless test particles of mass 1.0 that
     // every step() carries along on the bodies' own trees and that exert nothing.  A list of the
     // engine's own, kept across resetBodies; vx, vy empty: zeros; empty x, y: no tracers.

@@ -200,7 +200,7 @@ int bh_step(bh_engine *e, int32_t k);
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
  * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
- * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_find_neighbors, bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers, and
  * bh_set_step_log, bh_get_step_log and bh_get_step_log_phi.
@@ -328,6 +328,67 @@ int bh_compute_field(bh_engine *e, int64_t n_probe, const double *px, const doub
 /* HIP-event duration (ms) of the last field kernel launch (bh_compute_field; the probes' keying,
  * sort and upload are outside it); 0 before the first. */
 int bh_field_kernel_ms(const bh_engine *e, double *ms);
+
+/* Which bodies of the current state lie within a radius of n_probe points: counts, the nearest
+ * one, and the index lists.  The tree and the state semantics are exactly bh_compute_field's:
+ * the build with its jitter or the carried tree, always a full build on this engine, never a
+ * locally essential tree, not sharded; a tree-flag error is returned the same way; on a
+ * multi-device handle every member builds and member 0 answers; the probes never enter the
+ * engine's state: the call leaves what bh_compute_accelerations would leave.
+ * The candidate set S is the leaf sequence of bh_compute_field_direct: every non-empty leaf that
+ * lies under no mass-0 node.  So a body outside the root cell (or dropped from the tree by the
+ * jitter, BHA:126) is never found, a mass-0 body is never found, and a negative-mass body under
+ * a node of positive mass is found.
+ * Probe j has the radius rj = pr[j], or r if pr is NULL (r is then not used).  Body b of S is a
+ * neighbour of probe j iff
+ *     rj >= 0 && dx*dx + dy*dy <= rj*rj,   dx = x_b - px[j];  dy = y_b - py[j]
+ * in binary64, nothing fused, on the positions of the state after the call's build.  `<=` so that
+ * r = 0 finds coincident bodies; nothing is skipped by identity (a probe on a body finds it with
+ * d2 = 0); a NaN coordinate, or a NaN or negative radius in pr, finds nothing; +inf finds all of
+ * S; probes outside the root cell, at 2^40 or at 1e300 are legal.
+ *   count[j]       the number of neighbours of probe j;
+ *   nearest[j]     the caller index of the neighbour smallest under the order (d2, caller index),
+ *   d2_nearest[j]  and that d2 = dx*dx + dy*dy; -1 and +inf if there is none;
+ *   indices[offsets[j] .. offsets[j + 1])  the neighbours' caller indices, ascending;
+ *                  offsets[n_probe] and *n_total are the total.
+ * Caller indices are indices into the list bh_get_bodies returns after the call.  count, nearest,
+ * d2_nearest [n_probe] and n_total are each nullable; offsets [n_probe + 1] and indices [cap] are
+ * given both or neither.  If cap is less than the total the call returns BH_E_CAPACITY with
+ * count, nearest, d2_nearest, offsets and *n_total complete and indices untouched: one re-call
+ * with cap >= *n_total suffices (the re-call builds again, as every call does: where that build's
+ * jitter moves bodies once more, it answers for the state it leaves).  Lists of more than
+ * 2^31 - 1 entries in all are refused (BH_E_INVALID): ask in batches.
+ * Every output is an integer or a minimum under a total order -- no floating-point sum, no atomic
+ * on a float: two calls, two engines holding the same list, or a multi-device handle return
+ * identical bytes.  The walk prunes a cell by bh_neighbor_reach's bound (below), which changes
+ * the work, never the result.
+ * n_probe = 0 returns BH_OK after the build, launches nothing, leaves bh_neighbors_kernel_ms as
+ * it was and sets *n_total = 0 (and offsets[0] = 0).  With no body in the tree every count is 0
+ * and every offset 0.
+ * BH_E_INVALID (with bh_last_error text): e NULL, n_probe < 0 or > 2^28, px or py NULL with
+ * n_probe > 0, pr NULL and r NaN or negative, exactly one of offsets and indices given, cap < 0.
+ * BH_E_STATE between bh_step_begin and bh_step_end. */
+int bh_find_neighbors(bh_engine *e, int64_t n_probe, const double *px, const double *py,
+                      double r, const double *pr, int64_t *count, int64_t *nearest,
+                      double *d2_nearest, int64_t *offsets, int64_t *indices, int64_t cap,
+                      int64_t *n_total);
+
+/* HIP-event duration (ms) of the last bh_find_neighbors call's device work, from its first walk
+ * to its last kernel (the scan of the counts, the second walk and the segmented sort included;
+ * with lists it spans the host's read-back of the total between the two walks; the probes'
+ * keying, sort and upload are outside it); 0 before the first. */
+int bh_neighbors_kernel_ms(const bh_engine *e, double *ms);
+
+/* The pruning bound of bh_find_neighbors' walk for the root cell of these params (host-only: no
+ * device, no engine), returned by the function the kernel's host side itself uses (as
+ * bh_launch_plan's values are).  *reach = D_d for 0 <= depth < 40: in any tree an engine with
+ * this root cell can build, every body of S under a depth-d internal node lies within D_d of that
+ * node's (comX, comY), provided the node's mass lies in [2^-900, 2^k) with 2^k the power of two
+ * below DBL_MAX / (4 max |coordinate| of the root cell) -- the walk opens any other node
+ * unconditionally.  D_d = 2 sqrt(2) h_d (the cell's diagonal) + a jitter allowance + the centre
+ * of mass's rounding, all with a relative margin of 2^-40.
+ * BH_E_INVALID: p or reach NULL, depth outside 0..39, params without a valid root cell. */
+int bh_neighbor_reach(const bh_params *p, int32_t depth, double *reach);
 
 /* The exact field of the current state at n_probe points: bh_compute_field with no cell ever
  * accepted, whatever the engine's theta.  Arguments, probe semantics (a probe is not in the tree;
