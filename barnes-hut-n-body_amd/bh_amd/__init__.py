@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "bh_launch_plan", "bh_render_quads", "bh_render_quads_kernel_ms",
     "bh_compute_field", "bh_field_kernel_ms",
     "bh_find_neighbors", "bh_neighbors_kernel_ms", "bh_neighbor_reach",
+    "bh_find_groups", "bh_groups_kernel_ms",
     "bh_compute_field_direct", "bh_compute_force_error", "bh_direct_field_kernel_ms",
     "bh_direct_field_shape",
     "bh_compute_field_grid", "bh_field_grid_of_view", "bh_field_grid_kernel_ms",
@@ -110,6 +111,48 @@ class BhForceError(ctypes.Structure):
         ("mean_rel", ctypes.c_double),
         ("rms_rel", ctypes.c_double),
     ]
+
+
+class BhGroup(ctypes.Structure):
+    """struct bh_group (include/bh_engine.h) -- one group of bh_find_groups' catalogue."""
+    _fields_ = [
+        ("label", ctypes.c_int64),
+        ("count", ctypes.c_int64),
+        ("first", ctypes.c_int64),
+        ("mass", ctypes.c_double),
+        ("mx", ctypes.c_double),
+        ("my", ctypes.c_double),
+        ("px", ctypes.c_double),
+        ("py", ctypes.c_double),
+    ]
+
+
+class BhGroupsSummary(ctypes.Structure):
+    """struct bh_groups_summary (include/bh_engine.h)."""
+    _fields_ = [
+        ("n_bodies", ctypes.c_int64),
+        ("n_in_tree", ctypes.c_int64),
+        ("n_groups_all", ctypes.c_int64),
+        ("n_groups", ctypes.c_int64),
+        ("largest_label", ctypes.c_int64),
+        ("largest_count", ctypes.c_int64),
+    ]
+
+
+# bh_group as a numpy record (the same 64 bytes)
+GROUP_DTYPE = np.dtype([("label", "<i8"), ("count", "<i8"), ("first", "<i8"), ("mass", "<f8"),
+                        ("mx", "<f8"), ("my", "<f8"), ("px", "<f8"), ("py", "<f8")])
+
+
+@dataclass(frozen=True)
+class GroupsSummary:
+    """Engine.find_groups(): the fields of bh_groups_summary."""
+    n_bodies: int
+    n_in_tree: int
+    n_groups_all: int
+    n_groups: int
+    largest_label: int
+    largest_count: int
 
 
 @dataclass(frozen=True)
@@ -281,6 +324,10 @@ def load_library(path: str | None = None):
                                       _I64P, _D, _I64P, _I64P, ctypes.c_int64, _I64P]
     lib.bh_neighbors_kernel_ms.argtypes = [_VP, _D]
     lib.bh_neighbor_reach.argtypes = [ctypes.POINTER(BhParams), ctypes.c_int32, _D]
+    lib.bh_find_groups.argtypes = [_VP, ctypes.c_double, ctypes.c_int64, _I64P, ctypes.c_int64,
+                                   _I64P, ctypes.c_int64, ctypes.POINTER(BhGroup),
+                                   ctypes.c_int64, ctypes.POINTER(BhGroupsSummary)]
+    lib.bh_groups_kernel_ms.argtypes = [_VP, _D]
     lib.bh_compute_field_direct.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
     lib.bh_compute_force_error.argtypes = [_VP, ctypes.c_int64, _I64P, _D, _D, _D, _D,
                                            ctypes.POINTER(BhForceError)]
@@ -885,6 +932,43 @@ class Engine:
         last kernel (bh_neighbors_kernel_ms)."""
         return self._kernel_ms(self._lib.bh_neighbors_kernel_ms)
 
+    def find_groups(self, link, min_members=1, labels=True, members=False):
+        """bh_find_groups: the friends-of-friends groups of the bodies at linking length `link`.
+        Returns (summary, label, groups) and with members=True also the member array: label[i]
+        is the smallest list index of body i's group, -1 for a body that is not in the tree or
+        has mass 0 (None with labels=False); groups is a structured array (GROUP_DTYPE) of the
+        groups with at least min_members members in ascending label -- count, first, and the
+        fixed-order sums mass, mx, my, px, py; group g's members are
+        member_array[g.first:g.first + g.count], ascending.  Indices are into get_bodies() after
+        the call.  A build, exactly as find_neighbors (the jitter may move positions).  The
+        catalogue's size is learnt from a first call that asks for the summary alone."""
+        n = self.num_bodies()
+        sm = BhGroupsSummary()
+        rc = self._lib.bh_find_groups(self._h, float(link), int(min_members), None, 0, None, 0,
+                                      None, 0, ctypes.byref(sm))
+        self._check(rc)
+        for _ in range(2):  # (a build's jitter may change the sizes once more)
+            lab = np.empty(n, dtype=np.int64) if labels else None
+            mem = np.empty(max(n, 1), dtype=np.int64) if members else None
+            ncat = int(sm.n_groups)
+            cat = np.zeros(max(ncat, 1), dtype=GROUP_DTYPE)
+            i64 = lambda a: a.ctypes.data_as(_I64P) if a is not None else None  # noqa: E731
+            rc = self._lib.bh_find_groups(self._h, float(link), int(min_members), i64(lab), n,
+                                          i64(mem), n, cat.ctypes.data_as(ctypes.POINTER(BhGroup)),
+                                          ncat, ctypes.byref(sm))
+            if rc != BH_E_CAPACITY:
+                break
+        self._check(rc)
+        summary = GroupsSummary(int(sm.n_bodies), int(sm.n_in_tree), int(sm.n_groups_all),
+                                int(sm.n_groups), int(sm.largest_label), int(sm.largest_count))
+        out = (summary, lab, cat[:summary.n_groups].copy())
+        return out + (mem[:summary.n_in_tree].copy(),) if members else out
+
+    def groups_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last find_groups call's device work, link walk to last
+        catalogue kernel (bh_groups_kernel_ms)."""
+        return self._kernel_ms(self._lib.bh_groups_kernel_ms)
+
     def compute_field_direct(self, px, py, pm=None, want_accel=True, want_phi=True):
         """bh_compute_field_direct: compute_field with no cell ever accepted, whatever the
         engine's theta -- every non-empty leaf is summed, by a tiled all-pairs kernel.  Same
@@ -1399,6 +1483,23 @@ class PhysicsEngine:
         _, nearest, _ = self._eng.find_neighbors([float(x)], [float(y)], float(r), counts=False)
         self._pull()
         return self._bodies[int(nearest[0])] if nearest[0] >= 0 else None
+
+    def groups(self, link, min_members=2):
+        """The friends-of-friends groups of the caller's list at linking length `link`
+        (Engine.find_groups): a list of lists of the caller's own Body objects, one per group of
+        at least min_members members, in catalogue order (ascending lowest list index; within a
+        group ascending list index).  Builds a tree as step()'s first half does, so its jitter is
+        written back into the Body objects; bodies outside the root cell or of mass 0 are in no
+        group."""
+        self._eng.set_params(self._params())
+        if self._changed():
+            self._push()
+        _, _, cat, mem = self._eng.find_groups(float(link), int(min_members), labels=False,
+                                               members=True)
+        self._pull()
+        bs = self._bodies
+        return [[bs[int(c)] for c in mem[int(g["first"]):int(g["first"] + g["count"])]]
+                for g in cat]
 
     getBodies = get_bodies
     resetBodies = reset_bodies

@@ -808,6 +808,40 @@ hipError_t neighbors_sort(int64_t total, int64_t n, const int64_t *offsets, uint
                           uint32_t *idx_s, int bits, int64_t *out, void *scratch,
                           size_t &scratch_bytes, hipStream_t s);
 
+// ---- launchers (groups.hip): friends-of-friends groups of the leaf sequence ---------------
+// The working set of bh_find_groups for a list of n bodies (the engine allocates it).  The
+// union-find and the leaf planes are indexed by body slot or by leaf (n entries); the scans'
+// planes have n + 1 entries, the last for the total.
+struct GroupBufs {
+    uint32_t *parent, *minc;  // per body slot: the union-find; per root, the smallest caller index
+    uint32_t *rootof;         // per leaf: its root
+    uint64_t *key, *key_s;    // per leaf: (label << bits) | caller index, as made and sorted
+    uint32_t *val, *val_s;    // ... and the leaf it came from
+    uint32_t *flag, *gid;     // n + 1: run heads of the sorted keys and their exclusive scan
+    uint32_t *first;          // n + 1: where run g begins; first[runs] = the leaf count
+    uint32_t *keep, *kidx;    // n + 1: runs of at least min_members members, their scan
+    int64_t *label;           // n: label by caller index, -1 for a body not in S
+    int64_t *members;         // n: the caller indices of S by (label, caller index)
+    double *part;             // 5 planes of groups_partial_slots(n): the blocks' partial sums
+    bh_group *groups;         // n: the catalogue, compacted
+    int64_t *summary;         // the six fields of bh_groups_summary
+    void *scratch;            // groups_scratch_bytes(n): the sort and the scans
+    size_t scratch_bytes;
+};
+size_t groups_partial_slots(int64_t n);
+size_t groups_scratch_bytes(int64_t n);
+// parent[s] = s, minc[s] = none, label[i] = -1 (before the stopwatch)
+void groups_prepare(int64_t n, const GroupBufs &B, hipStream_t s);
+// The link walk over the leaf sequence (one lane per leaf; the launch shape is field_walk's for n
+// lanes, lanes beyond *d_count idle), then flattening, labels and the catalogue, all on the
+// stream: bodies a != b of the sequence are linked iff dx*dx + dy*dy <= link*link (binary64,
+// nothing fused, on the leaf records' positions).  vx, vy: the state's, in slot order.
+hipError_t groups_run(const Node *nodes, size_t node_cap, const uint32_t *d_T,
+                      const uint32_t *cidx, const LeafList &leaves, const uint32_t *d_count,
+                      const double *vx, const double *vy, int64_t n, double link,
+                      int64_t min_members, const NeighborReach &rc, const GroupBufs &B,
+                      hipStream_t s);
+
 // ---- launchers (render.hip) ------------------------------------------------------
 // The body pass of a frame (PNL:302-307).  Working planes `packed` and `cnt` (null: no density):
 // render_padded_pixels() uint32 each, zero on entry to render_raster and zero again after

@@ -276,6 +276,19 @@ struct bh_engine {
     void *nbr_sort = nullptr;      // the segmented sort's scratch
     size_t nbr_sort_bytes = 0;
     Stopwatch nbr_sw;  // from the first walk to the last kernel of the last call
+    // bh_find_groups (groups.hip): the call's own buffers, allocated on first use and grown when
+    // the list outgrows them (grp_cap bodies)
+    uint32_t *grp_u32 = nullptr;   // parent, minc, rootof, val, val_s; flag, gid, first, keep, kidx
+    uint64_t *grp_u64 = nullptr;   // key, sorted key
+    int64_t *grp_i64 = nullptr;    // label, members; the summary
+    double *grp_part = nullptr;    // the blocks' partial sums
+    bh_group *grp_groups = nullptr;
+    void *grp_scratch = nullptr;   // the sort and the scans
+    size_t grp_scratch_bytes = 0;
+    int64_t grp_cap = 0;
+    // from the link walk to the last catalogue kernel of the last call that found a non-empty S;
+    // a call records into grp_sw_run and the two change places once it knows S is not empty
+    Stopwatch grp_sw, grp_sw_run;
     // bh_set_tracers (field.hip k_tracer_step): the tracer list and its lane map.  Nothing is
     // allocated while the list is empty; every buffer is sized for exactly trc_n tracers and made
     // anew when the count changes (a stale lane map would index past the planes)
@@ -1948,6 +1961,72 @@ int neighbors_launch(bh_engine *e, NeighborQuery &q, bool tree) {
     }
     q.filled = q.lists && q.total <= q.cap;
     return e->nbr_sw.stop(e, e->stream);
+}
+
+// The planes of bh_find_groups' buffers for the engine's grp_cap.
+GroupBufs group_bufs(const bh_engine *e) {
+    const size_t cap = (size_t)e->grp_cap, cap1 = cap + 1;
+    GroupBufs B{};
+    uint32_t *u = e->grp_u32;
+    B.parent = u;
+    B.minc = u + cap;
+    B.rootof = u + 2 * cap;
+    B.val = u + 3 * cap;
+    B.val_s = u + 4 * cap;
+    u += 5 * cap;
+    B.flag = u;
+    B.gid = u + cap1;
+    B.first = u + 2 * cap1;
+    B.keep = u + 3 * cap1;
+    B.kidx = u + 4 * cap1;
+    B.key = e->grp_u64;
+    B.key_s = e->grp_u64 + cap;
+    B.label = e->grp_i64;
+    B.members = e->grp_i64 + cap;
+    B.summary = e->grp_i64 + 2 * cap;
+    B.part = e->grp_part;
+    B.groups = e->grp_groups;
+    B.scratch = e->grp_scratch;
+    B.scratch_bytes = e->grp_scratch_bytes;
+    return B;
+}
+
+// bh_find_groups on the tree ensure_tree() left: the leaf sequence, the velocities in this
+// build's slot order (a carried tree may have left them in the previous one), then the link walk
+// and the catalogue into the engine's own planes and the summary back to the host.  The host
+// reads nothing before the walk: lanes beyond the device-side leaf count idle.
+int groups_launch(bh_engine *e, double link, int64_t min_members, bh_groups_summary &sum) {
+    const int64_t n = e->n;
+    TRY(build_leaf_list(e));
+    TRY(materialize_velocities(e));
+    if (outgrown(e->grp_cap, e->grp_u32, n)) {
+        const size_t cap = (size_t)n;
+        TRY(dev_alloc(e, e->grp_u32, 10 * cap + 5));
+        TRY(dev_alloc(e, e->grp_u64, 2 * cap));
+        TRY(dev_alloc(e, e->grp_i64, 2 * cap + 6));
+        TRY(dev_alloc(e, e->grp_part, 5 * groups_partial_slots(n)));
+        TRY(dev_alloc(e, e->grp_groups, cap));
+        if (e->grp_scratch) (void)hipFree(e->grp_scratch);
+        e->grp_scratch = nullptr;
+        e->grp_scratch_bytes = groups_scratch_bytes(n);
+        HIPCHK(e, hipMalloc(&e->grp_scratch, e->grp_scratch_bytes ? e->grp_scratch_bytes : 1));
+        e->grp_cap = n;
+    }
+    // (the planes are laid out for grp_cap; the kernels run over the first n entries of each)
+    const GroupBufs B = group_bufs(e);
+    groups_prepare(n, B, e->stream);
+    HIPCHK(e, hipGetLastError());
+    TRY(e->grp_sw_run.start(e, e->stream));
+    HIPCHK(e, groups_run(e->nodes, e->node_cap, e->base + n, e->st.cidx, e->leaves, e->leaf_count,
+                         e->st.vx, e->st.vy, n, link, min_members, neighbor_reach_terms(e->geo), B,
+                         e->stream));
+    TRY(e->grp_sw_run.stop(e, e->stream));
+    int64_t h[6];
+    HIPCHK(e, hipMemcpyAsync(h, B.summary, sizeof(h), hipMemcpyDeviceToHost, e->stream));
+    SYNC(e, e->stream);
+    sum = bh_groups_summary{h[0], h[1], h[2], h[3], h[4], h[5]};
+    if (sum.n_in_tree > 0) std::swap(e->grp_sw, e->grp_sw_run);  // an empty S leaves the reading
+    return BH_OK;
 }
 
 int evaluate(bh_engine *e, uint32_t *visits, KickMode kick = KICK_NONE, bool *fused = nullptr,
@@ -3662,12 +3741,13 @@ void bh_destroy(bh_engine *e) {
                     e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats,
                     e->nbr_in, e->nbr_u32, e->nbr_i64, e->nbr_d2, e->nbr_scratch, e->nbr_idx,
                     e->nbr_list, e->nbr_sort,
+                    e->grp_u32, e->grp_u64, e->grp_i64, e->grp_part, e->grp_groups, e->grp_scratch,
                     e->trc, e->trc_snap, e->trc_u32, e->trc_scratch, e->slog_ring, e->slog_phi,
                     e->slog_stage, e->slog_part, e->slog_keep, e->slog_pos, e->slog_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
-    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->nbr_sw, &e->rnd_sw,
-                          &e->qd_sw})
+    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->nbr_sw, &e->grp_sw,
+                          &e->grp_sw_run, &e->rnd_sw, &e->qd_sw})
         sw->destroy();
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
@@ -4394,6 +4474,55 @@ int bh_find_neighbors(bh_engine *e, int64_t n_probe, const double *px, const dou
 
 int bh_neighbors_kernel_ms(const bh_engine *e, double *ms) {
     return kernel_ms(e, &bh_engine::nbr_sw, ms);
+}
+
+int bh_find_groups(bh_engine *e, double link, int64_t min_members, int64_t *label,
+                   int64_t label_cap, int64_t *members, int64_t members_cap, bh_group *groups,
+                   int64_t groups_cap, bh_groups_summary *summary) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    const char *bad = nullptr;
+    if (!(link >= 0.0)) bad = "link must be >= 0";
+    else if (min_members < 1) bad = "min_members must be >= 1";
+    else if (label_cap < 0) bad = "label_cap must be >= 0";
+    else if (members_cap < 0) bad = "members_cap must be >= 0";
+    else if (groups_cap < 0) bad = "groups_cap must be >= 0";
+    if (bad) {
+        e->err = std::string("bh_find_groups: ") + bad;
+        return BH_E_INVALID;
+    }
+    bh_groups_summary sum{0, 0, 0, 0, -1, 0};
+    const char *small = nullptr;  // the array whose cap is too small
+    TRY(query_call(e, [&](bh_engine *m, bool run) {
+        TRY(field_rank(m, run, [&](bool tree) {
+            return tree ? groups_launch(m, link, min_members, sum) : BH_OK;
+        }));
+        if (!run || m->n == 0) return BH_OK;
+        const int64_t N = m->n;
+        if (label && label_cap < N) small = "label_cap is below the number of bodies";
+        else if (members && members_cap < sum.n_in_tree) small = "members_cap is below n_in_tree";
+        else if (groups && groups_cap < sum.n_groups) small = "groups_cap is below n_groups";
+        if (small) return BH_OK;
+        const GroupBufs B = group_bufs(m);
+        auto out = [&](void *dst, const void *src, size_t bytes) {
+            if (dst && bytes) HIPCHK(m, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+            return BH_OK;
+        };
+        TRY(out(label, B.label, sizeof(int64_t) * (size_t)N));
+        TRY(out(members, B.members, sizeof(int64_t) * (size_t)sum.n_in_tree));
+        TRY(out(groups, B.groups, sizeof(bh_group) * (size_t)sum.n_groups));
+        return BH_OK;
+    }));
+    if (summary) *summary = sum;
+    if (small) {
+        e->err = std::string("bh_find_groups: ") + small + "; summary holds the sizes";
+        return BH_E_CAPACITY;
+    }
+    return BH_OK;
+}
+
+int bh_groups_kernel_ms(const bh_engine *e, double *ms) {
+    return kernel_ms(e, &bh_engine::grp_sw, ms);
 }
 
 int bh_neighbor_reach(const bh_params *p, int32_t depth, double *reach) {

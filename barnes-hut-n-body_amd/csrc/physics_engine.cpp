@@ -301,6 +301,27 @@ Body *PhysicsEngine::pick(double x, double y, double r) {
     return nearest >= 0 ? &(*bodies_)[(size_t)nearest] : nullptr;
 }
 
+std::vector<std::vector<Body *>> PhysicsEngine::groups(double link, int64_t minMembers) {
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    const int64_t n = (int64_t)bodies_->size();
+    // (no group has fewer than minMembers members, so n / minMembers records always suffice)
+    const int64_t room = minMembers >= 1 ? n / minMembers : 0;
+    std::vector<int64_t> members((size_t)n);
+    std::vector<bh_group> cat((size_t)room);
+    bh_groups_summary sum{};
+    check(bh_find_groups(eng_, link, minMembers, nullptr, 0, members.data(), n, cat.data(), room,
+                         &sum));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+    std::vector<std::vector<Body *>> out((size_t)sum.n_groups);
+    for (int64_t g = 0; g < sum.n_groups; ++g) {
+        out[(size_t)g].reserve((size_t)cat[(size_t)g].count);
+        for (int64_t k = 0; k < cat[(size_t)g].count; ++k)
+            out[(size_t)g].push_back(&(*bodies_)[(size_t)members[(size_t)(cat[(size_t)g].first + k)]]);
+    }
+    return out;
+}
+
 void PhysicsEngine::setTracers(const std::vector<double> &x, const std::vector<double> &y,
                                const std::vector<double> &vx, const std::vector<double> &vy) {
     const size_t n = x.size();

@@ -114,6 +114,14 @@ public:
     // does -- its jitter is written back into the list; the pointer is into that list.
     Body *pick(double x, double y, double r);
 
+    // The friends-of-friends groups of the caller's list at linking length `link`
+    // (bh_find_groups; no reference counterpart): one list of bodies per group of at least
+    // minMembers members, in catalogue order (ascending lowest list index; within a group
+    // ascending list index).  Bodies outside the root cell or of mass 0 are in no group.  Builds
+    // a tree as step()'s first half does -- its jitter is written back into the list; the
+    // pointers are into that list.
+    std::vector<std::vector<Body *>> groups(double link, int64_t minMembers = 2);
+
     // Tracers (bh_set_tracers; no reference counterpart): massless test particles of mass 1.0 that
     // every step() carries along on the bodies' own trees and that exert nothing.  A list of the
     // engine's own, kept across resetBodies; vx, vy empty: zeros; empty x, y: no tracers.

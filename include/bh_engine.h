@@ -200,7 +200,7 @@ int bh_step(bh_engine *e, int32_t k);
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
  * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
- * bh_find_neighbors, bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_find_neighbors, bh_find_groups, bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers, and
  * bh_set_step_log, bh_get_step_log and bh_get_step_log_phi.
@@ -389,6 +389,84 @@ int bh_neighbors_kernel_ms(const bh_engine *e, double *ms);
  * of mass's rounding, all with a relative margin of 2^-40.
  * BH_E_INVALID: p or reach NULL, depth outside 0..39, params without a valid root cell. */
 int bh_neighbor_reach(const bh_params *p, int32_t depth, double *reach);
+
+/* One group of bh_find_groups' catalogue. */
+typedef struct bh_group {
+    int64_t label;   /* smallest caller index among the group's members */
+    int64_t count;   /* members */
+    int64_t first;   /* members[first .. first + count) are this group's, ascending */
+    double mass, mx, my, px, py;   /* fixed-order sums, below */
+} bh_group;                        /* 64 bytes */
+
+typedef struct bh_groups_summary {
+    int64_t n_bodies;      /* N of the list after the call */
+    int64_t n_in_tree;     /* |S| */
+    int64_t n_groups_all;  /* components of S, singletons included */
+    int64_t n_groups;      /* those with count >= min_members */
+    int64_t largest_label; /* label of the group with the most members, the lower label on ties; -1 if S is empty */
+    int64_t largest_count; /* 0 if S is empty */
+} bh_groups_summary;
+
+/* The friends-of-friends groups of the current state: two bodies are friends if they are no
+ * farther apart than the linking length, a group is a connected component of that relation.
+ * Which clumps exist, what each weighs and where it is, without copying the bodies out.
+ * The tree and the state semantics are exactly bh_find_neighbors': the build with its jitter or
+ * the carried tree, always a full build on this engine, never a locally essential tree, not
+ * sharded; a tree-flag error is returned the same way; on a multi-device handle every member
+ * builds and member 0 answers; the call leaves what bh_compute_accelerations would leave.
+ * The candidate set S is bh_find_neighbors': the leaf sequence of bh_compute_field_direct, every
+ * non-empty leaf that lies under no mass-0 node.  So a body outside the root cell (or dropped
+ * from the tree by the jitter, BHA:126) and a mass-0 body are in no group, and a negative-mass
+ * body under a node of positive mass is in S.
+ * Bodies a != b of S are linked iff
+ *     dx*dx + dy*dy <= link*link,   dx = x_a - x_b;  dy = y_a - y_b
+ * in binary64, nothing fused, on the positions of the state after the call's build.  The relation
+ * is symmetric bit for bit (x_a - x_b is the exact negation of x_b - x_a).  `<=` so that link = 0
+ * links coincident bodies; +inf makes S one group.  A group is a connected component of the link
+ * graph on S; its label is the smallest caller index among its members.  Caller indices are
+ * indices into the list bh_get_bodies returns after the call.
+ * Outputs, each nullable with its cap (an array that is NULL is not asked for, whatever its cap):
+ *   label[i], i < N   the label of body i's group, or -1 for a body not in S; needs
+ *                     label_cap >= N;
+ *   members           the caller indices of S sorted by (label, caller index); needs
+ *                     members_cap >= n_in_tree (N always suffices);
+ *   groups            the groups with count >= min_members in ascending label, n_groups entries;
+ *                     needs groups_cap >= n_groups; `first` indexes members and is valid whether
+ *                     or not members was asked for;
+ *   summary           always complete when the call returns BH_OK or BH_E_CAPACITY.
+ * The sums of a group: its members in ascending caller index are c0 < c1 < ...; the term of
+ * member c is m, m*x, m*y, m*vx, m*vy for mass, mx, my, px, py -- each one binary64 multiply,
+ * never fused; x, y are the positions after the build, vx, vy the state's (a build does not touch
+ * them).  Block k holds members [256k, 256k + 256) of that list; its partial is the sequential
+ * sum of its terms in order from +0.0; the group's value is the sequential sum of the block
+ * partials in order from +0.0.  No floating-point atomic is used anywhere.
+ * Every output is an integer or such a sum: two calls, two engines holding the same list, or a
+ * multi-device handle return identical bytes.  The walk prunes a cell by bh_neighbor_reach's
+ * bound and the unions happen in whatever order the device runs them, which changes the work,
+ * never the result.
+ * If a given array's cap is too small the call returns BH_E_CAPACITY with summary complete and
+ * all three arrays untouched: one re-call with sufficient caps suffices (it builds again, as
+ * every call does: where that build's jitter moves bodies once more, it answers for the state it
+ * leaves).
+ * N = 0, or S empty: BH_OK, summary all zero (n_bodies too) except largest_label = -1, and
+ * bh_groups_kernel_ms left as it was; with bodies but an empty S the labels are all -1.  (With
+ * N = 0 nothing is launched; an empty S is found out on the device, whose kernels then idle.)
+ * Cost: the walk visits every friend of every body as a leaf, like bh_find_neighbors, so a call
+ * costs O(linked pairs); a linking length far above the mean separation of a dense scene is slow.
+ * Accepting a whole cell at once where its reach is small against link is left out on purpose
+ * (DESIGN.md §18), and so are unbinding, per-group angular momentum and groups of tracers.
+ * BH_E_INVALID (with bh_last_error text): e NULL, link NaN or negative, min_members < 1, a
+ * negative cap.  BH_E_STATE between bh_step_begin and bh_step_end. */
+int bh_find_groups(bh_engine *e, double link, int64_t min_members,
+                   int64_t *label,   int64_t label_cap,
+                   int64_t *members, int64_t members_cap,
+                   bh_group *groups, int64_t groups_cap,
+                   bh_groups_summary *summary);
+
+/* HIP-event duration (ms) of the last bh_find_groups call's own device work, from the link
+ * walk's start to the last catalogue kernel (the build, the leaf sequence and the copy-out are
+ * outside it); 0 before the first call that found a non-empty S. */
+int bh_groups_kernel_ms(const bh_engine *e, double *ms);
 
 /* The exact field of the current state at n_probe points: bh_compute_field with no cell ever
  * accepted, whatever the engine's theta.  Arguments, probe semantics (a probe is not in the tree;
