@@ -448,6 +448,21 @@ TraverseShape traverse_shape(size_t node_cap, int64_t lo, int64_t hi, int kick_m
 // them too).
 uint32_t bodies_per_wave(int64_t lanes);
 uint32_t waves_per_group(uint32_t waves, uint32_t bpw);
+// The launch of a query's walk over a list of `lanes` lanes by those two: the grid is `grid`
+// workgroups of `wpb` waves.  full_waves: 64 lanes per wave whatever the list's size.
+struct WalkShape {
+    uint32_t bpw, waves, wpb, grid;
+};
+WalkShape walk_shape(int64_t lanes, bool full_waves = false);
+// Whether the walks address node records by a 32-bit byte offset (cursor_walk.hpp nload_off): while
+// the array stays below the limit, 4 GiB.  (A diagnostic build with the limit 0 sends every walk
+// down the 64-bit address form, which no real tree of a test reaches.)
+#ifndef BH_NODE_OFF32_LIMIT
+#define BH_NODE_OFF32_LIMIT (size_t(1) << 32)
+#endif
+inline bool node_off32(size_t node_cap) {
+    return node_cap * sizeof(Node) < (size_t)(BH_NODE_OFF32_LIMIT);
+}
 void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x, double *y,
               const double *m, const uint32_t *cidx, int64_t lo, int64_t hi, const Geometry &g,
               const ForceParams &fp, double *a2, const TraverseCounters *cnt,

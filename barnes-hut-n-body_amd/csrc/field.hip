@@ -15,129 +15,48 @@
 // and a = F / pm (BHA:390-391), phi = -(G * s) (the term of bh_compute_potential).  This is what
 // the engine already computes for a body outside the root cell (BHA:126: not inserted, walked).
 //
-// The walk is traverse.hip's walk(): one lane = one probe, one wave-shared pre-order cursor, the
-// node record through a scalar load requested one stop ahead, every lane's own criterion by
-// ballot.  It is a walk of its own because a probe has no slot: walk<false> skips the leaf whose
-// body slot equals the lane's slot and k_potential compares every leaf against it, while probe i
-// must feel the body in slot i; and the fast force walk relies on the own leaf's term being +-0,
-// while a probe that sits on a body owes that body's full potential term m / sqrt(soft2).  So no
-// path here compares a leaf with anything, and no term is ever excused.
+// The walk is the probe walk of cursor_walk.hpp (probe_walk, shared with potential.hip) for a lane
+// without a slot: one lane = one probe, one wave-shared pre-order cursor, every lane's own
+// criterion by ballot.  It is not the force walk because a probe has no slot: walk<false> skips
+// the leaf whose body slot equals the lane's slot and k_potential compares every leaf against it,
+// while probe i must feel the body in slot i; and the fast force walk relies on the own leaf's
+// term being +-0, while a probe that sits on a body owes that body's full potential term
+// m / sqrt(soft2).  So no path here compares a leaf with anything, and no term is ever excused.
 // One point-force block serves both results: the potential's term reuses the block's invR (one
 // multiply and one add more; never fused: the build contracts nothing).
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "bh_device.hpp"
-#include "fastmath.hpp"
+#include "cursor_walk.hpp"
 
 namespace bh {
 namespace {
 
-constexpr int TB = 64;
-constexpr int MAX_WPB = 8;           // waves per workgroup (traverse.hip waves_per_group)
-constexpr uint32_t FLD_XCD_RUN = 64; // consecutive waves per XCD (traverse.hip BH_TRAV_XCD_RUN)
-static_assert(FLD_XCD_RUN % MAX_WPB == 0, "an XCD run holds whole workgroups");
 constexpr int KEY_TB = 256;
 
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-
-// Node record through an explicit scalar load whose wait is placed by hand (traverse.hip nload).
-__device__ __forceinline__ u32x8 nload(const Node *p) {
-    u32x8 v;
-    asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
-__device__ __forceinline__ u32x8 nload_off(const Node *base, uint32_t idx) {
-    u32x8 v;
-    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(base), "s"(idx << 5) : "memory");
-    return v;
-}
-__device__ __forceinline__ void nwait(u32x8 &v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v)); }
-__device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// FAST: the wave's operands are inside the range guards of fastmath.hpp (fast_s2_ok,
-// lane_fast_ok) and every lane's G * pm is finite: the seeded sqrt / reciprocal sequences equal
-// the IEEE operations and the criterion's s2 is formed by an exponent subtraction.  A massless
-// node then needs no test, as in walk(): it carries the leaf flag (bh_device.hpp NODE_SKIP), so
-// the cursor moves past its subtree, and its terms -- f = (G pm) * 0 * invR2, 0 * invR, all
-// factors finite -- are exact +-0 that leave the sums (from +0.0, never -0.0) unchanged.
-// lane_self_ok has no counterpart: a coincident body's term is owed, whatever it is, and both
-// paths compute it with the same operations.
-template <bool FAST, bool OFF32>
-__device__ __forceinline__ void field_walk_wave(const Node *__restrict__ nodes, uint32_t T,
-                                                double bx, double by, double Gm, double soft2,
-                                                double theta2, double s2root, uint32_t resume,
-                                                double &fx, double &fy, double &s) {
-    uint32_t cur = 0;
-    // one iteration on record `rec`; the next record is requested into `nrec` (the node array
-    // has slack beyond T, so loading node T is harmless)
-    auto iter = [&](const u32x8 &rec, u32x8 &nrec) __attribute__((always_inline)) {
-        const double comX = as_f64(rec[0], rec[1]), comY = as_f64(rec[2], rec[3]);
-        const double mass = as_f64(rec[4], rec[5]);
-        uint32_t meta = rec[7];
-        asm volatile("" : "+s"(meta));  // keep the flag tests scalar
-        uint32_t next = rec[6];
-        next = next > cur ? next : cur + 1;  // structural guard: the cursor always advances
-        if (!FAST && (meta & NODE_SKIP)) {   // mass == 0.0 (BHA:216): not visited
-            cur = next;
-            nrec = OFF32 ? nload_off(nodes, cur) : nload(nodes + cur);
-            nwait(nrec);
-            return;
-        }
-        const uint64_t act_m = __builtin_amdgcn_ballot_w64(cur >= resume);
-        const double dx = comX - bx;  // BHA:223-225 == BHA:251-253
-        const double dy = comY - by;
-        const double d2 = dx * dx + dy * dy + soft2;
-        uint64_t contrib_m, open_m;  // lanes that take / open this node
-        if (meta & NODE_LEAF) {      // a probe is in no leaf: every non-empty leaf is taken
-            contrib_m = act_m;
-            open_m = 0;
-        } else {  // BHA:226-228, decided exactly as traverse.hip's walk decides it
-            uint64_t acc_m;
-            if (FAST) {
-                const uint64_t s2b = (uint64_t)__double_as_longlong(s2root) -
-                                     ((uint64_t)(meta & NODE_DEPTH2_MASK) << 52);
-                acc_m = __builtin_amdgcn_ballot_w64(__longlong_as_double((long long)s2b) <
-                                                    theta2 * d2);
-            } else {
-                const double t2 = __builtin_ldexp(theta2 * d2, (int)(meta & NODE_DEPTH2_MASK));
-                acc_m = __builtin_amdgcn_ballot_w64(s2root < t2);
-            }
-            contrib_m = act_m & acc_m;
-            open_m = act_m & ~acc_m;
-        }
-        const uint32_t ncur = open_m != 0ull ? cur + 1 : next;  // descend iff some lane opened
-        nrec = OFF32 ? nload_off(nodes, ncur) : nload(nodes + ncur);
-        if (__builtin_amdgcn_inverse_ballot_w64(contrib_m)) {  // BHA:250-259, order as written
-            double invR, invR2;
-            if (FAST) {
-                double h;
-                const double r = sqrt_rn_inrange_h(d2, h);
-                invR = rcp_rn_seeded(r, h + h);
-                invR2 = rcp_rn_seeded(d2, invR * invR);
-            } else {
-                invR = 1.0 / sqrt(d2);
-                invR2 = 1.0 / d2;
-            }
-            const double f = Gm * mass * invR2;
-            fx += f * dx * invR;
-            fy += f * dy * invR;
-            s += mass * invR;  // bh_compute_potential's term, from the block's own invR
-            resume = next;
-        }
-        nwait(nrec);
-        cur = ncur;
-    };
-    if (T == 0) return;  // no body inside the root cell: an empty tree
-    u32x8 r0 = nload(nodes), r1;
-    nwait(r0);
-    while (true) {
-        iter(r0, r1);
-        if (cur >= T) break;
-        iter(r1, r0);
-        if (cur >= T) break;
-    }
+// What the three walking kernels do between a lane's point and its sums: the guards of the fast
+// path over the wave's valid lanes, then the fast or the exact probe walk.  d_T null: no tree was
+// built (no bodies).  The sums start at +0.0; an invalid lane never becomes active.
+template <bool OFF32, int SUMS>
+__device__ __forceinline__ void probe_eval(const Node *__restrict__ nodes,
+                                           const uint32_t *__restrict__ d_T,
+                                           const ForceParams &fp, double s2root, double bx,
+                                           double by, double bm, bool valid, double &fx,
+                                           double &fy, double &s) {
+    const double Gm = fp.G * bm;  // (Config.G * b.m) is evaluated first (BHA:256)
+    const double soft2 = fp.soft2, theta2 = fp.theta2;
+    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
+    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
+    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
+                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
+    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
+    fx = fy = s = 0.0;
+    if (fast)
+        probe_walk<true, OFF32, false, SUMS>(nodes, T, bx, by, Gm, soft2, theta2, s2root, 0u,
+                                             resume, fx, fy, s);
+    else
+        probe_walk<false, OFF32, false, SUMS>(nodes, T, bx, by, Gm, soft2, theta2, s2root, 0u,
+                                              resume, fx, fy, s);
 }
 
 // Wave v walks the bpw lanes [bpw v, bpw v + bpw); lane q holds probe order[q] and writes its
@@ -154,12 +73,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_field(const Node *__restrict__
                                                         double *__restrict__ ay,
                                                         double *__restrict__ phi, uint32_t bpw,
                                                         uint32_t wpb) {
-    uint32_t b = blockIdx.x;  // runs of FLD_XCD_RUN consecutive waves per XCD (bh_device.hpp)
-    {
-        const uint32_t C = FLD_XCD_RUN / wpb, G = 8 * C, full = gridDim.x / G;
-        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
-    }
-    const uint32_t v = b * wpb + (threadIdx.x >> 6);
+    const uint32_t v = xcd_run_wave(wpb);
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t q = (int64_t)v * bpw + lane;
     const bool valid = lane < bpw && q < n;
@@ -167,20 +81,8 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_field(const Node *__restrict__
     const double bx = valid ? px[j] : 0.0;
     const double by = valid ? py[j] : 0.0;
     const double bm = valid && pm ? pm[j] : 1.0;
-    const double Gm = fp.G * bm;  // (Config.G * b.m) is evaluated first (BHA:256)
-    const double soft2 = fp.soft2, theta2 = fp.theta2;
-    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
-    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
-    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
-                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
-    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
-    double fx = 0.0, fy = 0.0, s = 0.0;
-    if (fast)
-        field_walk_wave<true, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
-                                     s);
-    else
-        field_walk_wave<false, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
-                                      s);
+    double fx, fy, s;
+    probe_eval<OFF32, PROBE_BOTH>(nodes, d_T, fp, s2root, bx, by, bm, valid, fx, fy, s);
     if (!valid) return;
     ax[j] = fx / bm;  // BHA:390-391
     ay[j] = fy / bm;
@@ -192,7 +94,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_field(const Node *__restrict__
 // exact); instead of storing a and phi the lane applies the leapfrog's lines to its own tracer in
 // registers -- KICK_DRIFT = BHA:414-422, KICK_ONLY = BHA:429-432, the operations of k_kick_drift /
 // k_kick in their order, never fused -- and writes the tracer's values back in place, by list
-// index.  The potential's sum is not used here, so its multiply and add are dropped with it.
+// index.  The potential's sum is not used here, so the walk is asked for the force alone.
 template <int KICK, bool OFF32>
 __global__ __launch_bounds__(TB * MAX_WPB) void k_tracer_step(const Node *__restrict__ nodes,
                                                               const uint32_t *__restrict__ d_T,
@@ -206,32 +108,15 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_tracer_step(const Node *__rest
                                                               double dt, uint32_t bpw,
                                                               uint32_t wpb) {
     static_assert(KICK == KICK_DRIFT || KICK == KICK_ONLY, "a tracer walk always kicks");
-    uint32_t b = blockIdx.x;  // runs of FLD_XCD_RUN consecutive waves per XCD (bh_device.hpp)
-    {
-        const uint32_t C = FLD_XCD_RUN / wpb, G = 8 * C, full = gridDim.x / G;
-        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
-    }
-    const uint32_t v = b * wpb + (threadIdx.x >> 6);
+    const uint32_t v = xcd_run_wave(wpb);
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t q = (int64_t)v * bpw + lane;
     const bool valid = lane < bpw && q < n;
     const int64_t j = valid ? (int64_t)order[q] : 0;  // the tracer's list index
     const double bx = valid ? tx[j] : 0.0;
     const double by = valid ? ty[j] : 0.0;
-    const double Gm = fp.G * 1.0;  // (Config.G * b.m) is evaluated first (BHA:256)
-    const double soft2 = fp.soft2, theta2 = fp.theta2;
-    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
-    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
-    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
-                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
-    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
-    double fx = 0.0, fy = 0.0, s = 0.0;
-    if (fast)
-        field_walk_wave<true, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
-                                     s);
-    else
-        field_walk_wave<false, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
-                                      s);
+    double fx, fy, s;
+    probe_eval<OFF32, PROBE_FORCE>(nodes, d_T, fp, s2root, bx, by, 1.0, valid, fx, fy, s);
     if (!valid) return;
     const double ax = fx / 1.0;  // BHA:390-391
     const double ay = fy / 1.0;
@@ -274,12 +159,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_field_grid(const Node *__restr
                                                              double *__restrict__ ay,
                                                              double *__restrict__ phi,
                                                              FieldGridShape sh) {
-    uint32_t b = blockIdx.x;  // runs of FLD_XCD_RUN consecutive waves per XCD (bh_device.hpp)
-    {
-        const uint32_t C = FLD_XCD_RUN / sh.wpb, G = 8 * C, full = gridDim.x / G;
-        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
-    }
-    const uint32_t v = __builtin_amdgcn_readfirstlane(b * sh.wpb + (threadIdx.x >> 6));
+    const uint32_t v = __builtin_amdgcn_readfirstlane(xcd_run_wave(sh.wpb));
     if (v >= sh.tiles) return;  // (the last workgroup's spare waves)
     uint32_t tx, ty;
     zorder_tile(v, sh.tiles_x, sh.tiles_y, tx, ty);
@@ -289,20 +169,8 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_field_grid(const Node *__restr
     const bool valid = ly < sh.tile_h && c < (uint32_t)g.nx && r < (uint32_t)g.ny;
     const double bx = valid ? g.x0 + (double)c * g.dx : 0.0;
     const double by = valid ? g.y0 + (double)r * g.dy : 0.0;
-    const double Gm = fp.G * 1.0;
-    const double soft2 = fp.soft2, theta2 = fp.theta2;
-    const uint32_t resume = valid ? 0u : 0xFFFFFFFFu;  // active at `cur` iff cur >= resume
-    const uint32_t T = d_T ? __builtin_amdgcn_readfirstlane(*d_T) : 0u;
-    const bool lane_ok = lane_fast_ok(bx, by, soft2) &&
-                         __builtin_fabs(Gm) <= 1.7976931348623157e308;  // (false for a NaN)
-    const bool fast = fast_s2_ok(s2root) && __ballot(valid && !lane_ok) == 0ull;
-    double fx = 0.0, fy = 0.0, s = 0.0;
-    if (fast)
-        field_walk_wave<true, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
-                                     s);
-    else
-        field_walk_wave<false, OFF32>(nodes, T, bx, by, Gm, soft2, theta2, s2root, resume, fx, fy,
-                                      s);
+    double fx, fy, s;
+    probe_eval<OFF32, PROBE_BOTH>(nodes, d_T, fp, s2root, bx, by, 1.0, valid, fx, fy, s);
     if (!valid) return;
     const int64_t j = (int64_t)r * g.nx + c;
     if (ax) ax[j] = fx / 1.0;  // BHA:390-391
@@ -408,10 +276,9 @@ FieldGridShape field_grid_shape(int32_t nx, int32_t ny) {
 void field_grid_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T,
                      const bh_field_grid &g, const Geometry &geo, const ForceParams &fp, double *ax,
                      double *ay, double *phi, hipStream_t s) {
-    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
     const FieldGridShape sh = field_grid_shape(g.nx, g.ny);
     const unsigned grid = (sh.tiles + sh.wpb - 1) / sh.wpb;
-    if (off32)
+    if (node_off32(node_cap))
         k_field_grid<true><<<grid, TB * sh.wpb, 0, s>>>(nodes, d_T, g, fp, geo.s2[0], ax, ay, phi,
                                                         sh);
     else
@@ -456,17 +323,13 @@ void field_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const d
                 const Geometry &g, const ForceParams &fp, double *ax, double *ay, double *phi,
                 hipStream_t s) {
     if (n <= 0) return;
-    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
-    const uint32_t bpw = bodies_per_wave(n);
-    const uint32_t waves = (uint32_t)((n + bpw - 1) / bpw);
-    const uint32_t wpb = waves_per_group(waves, bpw);
-    const unsigned grid = (waves + wpb - 1) / wpb;
-    if (off32)
-        k_field<true><<<grid, TB * wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0], ax,
-                                                ay, phi, bpw, wpb);
+    const WalkShape w = walk_shape(n);
+    if (node_off32(node_cap))
+        k_field<true><<<w.grid, TB * w.wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0],
+                                                    ax, ay, phi, w.bpw, w.wpb);
     else
-        k_field<false><<<grid, TB * wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0],
-                                                 ax, ay, phi, bpw, wpb);
+        k_field<false><<<w.grid, TB * w.wpb, 0, s>>>(nodes, d_T, px, py, pm, order, n, fp, g.s2[0],
+                                                     ax, ay, phi, w.bpw, w.wpb);
 }
 
 #ifndef BH_TRACER_REORDER
@@ -480,10 +343,11 @@ void field_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const d
 static_assert(BH_TRACER_REORDER >= 1, "the lane map is re-made every R >= 1 steps");
 
 TracerShape tracer_shape(int64_t n) {
+    const WalkShape w = walk_shape(n);
     TracerShape sh;
-    sh.bpw = bodies_per_wave(n);
-    sh.waves = (uint32_t)((n + sh.bpw - 1) / sh.bpw);
-    sh.wpb = waves_per_group(sh.waves, sh.bpw);
+    sh.bpw = w.bpw;
+    sh.waves = w.waves;
+    sh.wpb = w.wpb;
     sh.reorder = BH_TRACER_REORDER;
     return sh;
 }
@@ -492,7 +356,7 @@ void tracer_step(const Node *nodes, size_t node_cap, const uint32_t *d_T, double
                  double *tvx, double *tvy, const uint32_t *order, int64_t n, const Geometry &g,
                  const ForceParams &fp, KickMode kick, double dtHalf, double dt, hipStream_t s) {
     if (n <= 0) return;
-    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
+    const bool off32 = node_off32(node_cap);
     const TracerShape sh = tracer_shape(n);
     const unsigned grid = (sh.waves + sh.wpb - 1) / sh.wpb, tb = TB * sh.wpb;
 #define BH_TRACER_LAUNCH(K, O)                                                                    \

@@ -120,8 +120,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_groups_link(
     const Node *__restrict__ nodes, const uint32_t *__restrict__ d_T,
     const double *__restrict__ leaves, const uint32_t *__restrict__ d_count, double link,
     NeighborReach rc, uint32_t *parent, uint32_t bpw, uint32_t wpb) {
-    const uint32_t b = nbr_xcd_block(blockIdx.x, wpb);
-    const uint32_t v = b * wpb + (threadIdx.x >> 6);
+    const uint32_t v = xcd_run_wave(wpb);
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t q = (int64_t)v * bpw + lane;
     const uint32_t nl = __builtin_amdgcn_readfirstlane(*d_count);
@@ -364,17 +363,13 @@ hipError_t groups_run(const Node *nodes, size_t node_cap, const uint32_t *d_T,
                       hipStream_t s) {
     if (n <= 0) return hipSuccess;
     {  // the link walk, in the launch shape the other walks choose for n lanes
-        const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
-        const uint32_t bpw = bodies_per_wave(n);
-        const uint32_t waves = (uint32_t)((n + bpw - 1) / bpw);
-        const uint32_t wpb = waves_per_group(waves, bpw);
-        const unsigned grid = (waves + wpb - 1) / wpb;
-        if (off32)
-            k_groups_link<true><<<grid, TB * wpb, 0, s>>>(nodes, d_T, leaves.rec, d_count, link, rc,
-                                                          B.parent, bpw, wpb);
+        const WalkShape w = walk_shape(n);
+        if (node_off32(node_cap))
+            k_groups_link<true><<<w.grid, TB * w.wpb, 0, s>>>(nodes, d_T, leaves.rec, d_count,
+                                                              link, rc, B.parent, w.bpw, w.wpb);
         else
-            k_groups_link<false><<<grid, TB * wpb, 0, s>>>(nodes, d_T, leaves.rec, d_count, link,
-                                                           rc, B.parent, bpw, wpb);
+            k_groups_link<false><<<w.grid, TB * w.wpb, 0, s>>>(nodes, d_T, leaves.rec, d_count,
+                                                               link, rc, B.parent, w.bpw, w.wpb);
     }
     const int bits = key_bits(n);
     const size_t slots = groups_partial_slots(n);

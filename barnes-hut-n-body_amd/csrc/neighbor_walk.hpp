@@ -2,8 +2,8 @@
 // (neighbors.hip: one lane = one probe) and bh_find_groups (groups.hip: one lane = one leaf).
 // Device code only; every name is local to the including file.
 //
-// The walk is field.hip's field_walk_wave: one wave-shared pre-order cursor, the node record
-// through a scalar load requested one stop ahead, every lane's own decision by ballot.  An
+// The walk is a stop of cursor_walk.hpp's cursor_walk: one wave-shared pre-order cursor, the node
+// record through a scalar load requested one stop ahead, every lane's own decision by ballot.  An
 // internal node of depth d is opened by a lane iff dist2(COM, lane) <= (r_lane pad + reach_d)^2,
 // where reach_d (neighbor_reach_at) bounds the distance from the node's COM to every leaf under
 // it.  The bound holds for a node whose mass lies in the range the COM's rounding analysis covers;
@@ -13,41 +13,12 @@
 #pragma once
 
 #include "bh_device.hpp"
+#include "cursor_walk.hpp"
 
 namespace bh {
 namespace {
 
-constexpr int TB = 64;
-constexpr int MAX_WPB = 8;           // waves per workgroup (traverse.hip waves_per_group)
-constexpr uint32_t NBR_XCD_RUN = 64; // consecutive waves per XCD (field.hip FLD_XCD_RUN)
-static_assert(NBR_XCD_RUN % MAX_WPB == 0, "an XCD run holds whole workgroups");
 constexpr uint32_t NBR_NONE = 0xFFFFFFFFu;  // no neighbour yet: above every caller index
-
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-
-// Node record through an explicit scalar load whose wait is placed by hand (traverse.hip nload).
-__device__ __forceinline__ u32x8 nload(const Node *p) {
-    u32x8 v;
-    asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
-__device__ __forceinline__ u32x8 nload_off(const Node *base, uint32_t idx) {
-    u32x8 v;
-    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(base), "s"(idx << 5) : "memory");
-    return v;
-}
-__device__ __forceinline__ void nwait(u32x8 &v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v)); }
-__device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
-
-// Workgroup b of a launch of wpb-wave workgroups -> the workgroup whose waves it walks: runs of
-// NBR_XCD_RUN consecutive waves per XCD (bh_device.hpp); the last, partial round keeps its order.
-__device__ __forceinline__ uint32_t nbr_xcd_block(uint32_t b, uint32_t wpb) {
-    const uint32_t C = NBR_XCD_RUN / wpb, G = 8 * C, full = gridDim.x / G;
-    if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
-    return b;
-}
 
 // What a walk keeps per lane.  NBR_COUNT: the number found.  NBR_NEAREST: that and the smallest
 // (d2, caller index).  NBR_PICK: the smallest alone, and the lane shrinks its radius to the best
@@ -77,29 +48,19 @@ __device__ __forceinline__ void nbr_walk_wave(const Node *__restrict__ nodes, ui
                                               const uint32_t *__restrict__ cidx,
                                               const NeighborReach rc, NbrLane &L,
                                               Link link = Link()) {
-    uint32_t cur = 0;
-    // one iteration on record `rec`; the next record is requested into `nrec` (the node array
-    // has slack beyond T, so loading node T is harmless)
-    auto iter = [&](const u32x8 &rec, u32x8 &nrec) __attribute__((always_inline)) {
-        const double comX = as_f64(rec[0], rec[1]), comY = as_f64(rec[2], rec[3]);
-        uint32_t meta = rec[7], mhi = rec[5];
-        asm volatile("" : "+s"(meta), "+s"(mhi));  // keep the flag and mass-range tests scalar
-        uint32_t next = rec[6];
-        next = next > cur ? next : cur + 1;  // structural guard: the cursor always advances
-        if (meta & NODE_SKIP) {              // mass == 0.0 (BHA:216): nothing under it is in S
-            cur = next;
-            nrec = OFF32 ? nload_off(nodes, cur) : nload(nodes + cur);
-            nwait(nrec);
-            return;
-        }
+    cursor_walk<OFF32, true>(nodes, T, [&](const CursorStop<OFF32> &st)
+                                           __attribute__((always_inline)) {
+        uint32_t mhi = st.mass_hi;
+        asm volatile("" : "+s"(mhi));  // keep the mass-range test scalar
+        const uint32_t meta = st.meta, next = st.next, cur = st.cur;
         const bool active = cur >= L.resume;
-        const double dx = comX - L.bx;
-        const double dy = comY - L.by;
+        const double dx = st.comX - L.bx;
+        const double dy = st.comY - L.by;
         const double d2 = dx * dx + dy * dy;
         if (meta & NODE_LEAF) {  // the record is the body: the exact test
             const bool hit = active && d2 <= L.r2;
             const uint64_t hit_m = __builtin_amdgcn_ballot_w64(hit);
-            nrec = OFF32 ? nload_off(nodes, next) : nload(nodes + next);
+            st.fetch(next);
             if (hit_m != 0ull) {
                 if (MODE == NBR_LINK) {
                     if (hit) link(meta & NODE_BODY_MASK);
@@ -122,9 +83,7 @@ __device__ __forceinline__ void nbr_walk_wave(const Node *__restrict__ nodes, ui
                     }
                 }
             }
-            nwait(nrec);
-            cur = next;
-            return;
+            return next;
         }
         // internal: prune iff the node's mass is in the covered range and the COM is farther than
         // the padded radius plus the depth's reach; a NaN d2 or threshold never prunes
@@ -134,20 +93,10 @@ __device__ __forceinline__ void nbr_walk_wave(const Node *__restrict__ nodes, ui
         const bool prune = covered && d2 > t * t;
         const uint64_t open_m = __builtin_amdgcn_ballot_w64(active && !prune);
         const uint32_t ncur = open_m != 0ull ? cur + 1 : next;  // descend iff some lane opened
-        nrec = OFF32 ? nload_off(nodes, ncur) : nload(nodes + ncur);
+        st.fetch(ncur);
         if (active && prune) L.resume = next;  // parked until the cursor has left the subtree
-        nwait(nrec);
-        cur = ncur;
-    };
-    if (T == 0) return;  // no body inside the root cell: an empty tree
-    u32x8 r0 = nload(nodes), r1;
-    nwait(r0);
-    while (true) {
-        iter(r0, r1);
-        if (cur >= T) break;
-        iter(r1, r0);
-        if (cur >= T) break;
-    }
+        return ncur;
+    });
 }
 
 }  // namespace

@@ -7,13 +7,12 @@
 // in binary64, nothing fused (the build contracts nothing).  A leaf record's comX / comY are its
 // body's position, so the test is made on the record itself.
 //
-// The walk (neighbor_walk.hpp, shared with groups.hip) is field.hip's field_walk_wave: one lane =
-// one probe, one wave-shared pre-order cursor, the node record through a scalar load requested
-// one stop ahead, every lane's own decision by ballot.  The opening criterion has another
-// right-hand side: an internal node of depth d is opened by a lane iff
-// dist2(COM, probe) <= (r_lane pad + reach_d)^2, where reach_d (neighbor_reach_at) bounds the
-// distance from the node's COM to every leaf under it.  The bound
-// holds for a node whose mass lies in the range the COM's rounding analysis covers; any other node
+// The walk (neighbor_walk.hpp, shared with groups.hip) is a stop of cursor_walk.hpp's shared
+// cursor walk, as the field's is: one lane = one probe, one wave-shared pre-order cursor, the node
+// record through a scalar load requested one stop ahead, every lane's own decision by ballot.
+// The opening criterion has another right-hand side: an internal node of depth d is opened by a
+// lane iff dist2(COM, probe) <= (r_lane pad + reach_d)^2, where reach_d (neighbor_reach_at) bounds
+// the distance from the node's COM to every leaf under it.  The bound holds for a node whose mass lies in the range the COM's rounding analysis covers; any other node
 // is opened by every active lane (opening is always safe).  dist2 carries no soft2: it is a
 // distance, not a force denominator.  Every path tests NODE_SKIP: a hit is not a term, so nothing
 // here may rely on a massless node adding +-0.
@@ -39,8 +38,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_neighbors(
     const uint32_t *__restrict__ order, int64_t n, NeighborReach rc, int64_t *__restrict__ count,
     int64_t *__restrict__ nearest, double *__restrict__ d2n, const int64_t *__restrict__ offsets,
     uint32_t *__restrict__ idx, uint32_t bpw, uint32_t wpb) {
-    const uint32_t b = nbr_xcd_block(blockIdx.x, wpb);
-    const uint32_t v = b * wpb + (threadIdx.x >> 6);
+    const uint32_t v = xcd_run_wave(wpb);
     const uint32_t lane = threadIdx.x & 63u;
     const int64_t q = (int64_t)v * bpw + lane;
     const bool valid = lane < bpw && q < n;
@@ -90,19 +88,15 @@ void nbr_launch(const Node *nodes, size_t node_cap, const uint32_t *d_T, const u
                 int64_t *nearest, double *d2n, const int64_t *offsets, uint32_t *idx,
                 hipStream_t s) {
     if (n <= 0) return;
-    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
-    const uint32_t bpw = bodies_per_wave(n);
-    const uint32_t waves = (uint32_t)((n + bpw - 1) / bpw);
-    const uint32_t wpb = waves_per_group(waves, bpw);
-    const unsigned grid = (waves + wpb - 1) / wpb;
-    if (off32)
-        k_neighbors<MODE, true><<<grid, TB * wpb, 0, s>>>(nodes, d_T, cidx, px, py, pr, r, order,
-                                                          n, rc, count, nearest, d2n, offsets,
-                                                          idx, bpw, wpb);
+    const WalkShape w = walk_shape(n);
+    if (node_off32(node_cap))
+        k_neighbors<MODE, true><<<w.grid, TB * w.wpb, 0, s>>>(nodes, d_T, cidx, px, py, pr, r,
+                                                              order, n, rc, count, nearest, d2n,
+                                                              offsets, idx, w.bpw, w.wpb);
     else
-        k_neighbors<MODE, false><<<grid, TB * wpb, 0, s>>>(nodes, d_T, cidx, px, py, pr, r, order,
-                                                           n, rc, count, nearest, d2n, offsets,
-                                                           idx, bpw, wpb);
+        k_neighbors<MODE, false><<<w.grid, TB * w.wpb, 0, s>>>(nodes, d_T, cidx, px, py, pr, r,
+                                                               order, n, rc, count, nearest, d2n,
+                                                               offsets, idx, w.bpw, w.wpb);
 }
 
 }  // namespace

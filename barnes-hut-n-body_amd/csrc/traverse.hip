@@ -18,56 +18,12 @@
 // Small lists (bfs_walk below): the first walk of a step over <= 4 096 bodies serves one body
 // per wave and examines the tree level by level, the terms added in pre-order -- the same sum.
 #include "bh_device.hpp"
+#include "cursor_walk.hpp"
 #include "fastmath.hpp"
 #include "open_threshold.hpp"
 
 namespace bh {
 namespace {
-
-// Workgroups in runs of BH_TRAV_XCD_RUN consecutive waves per XCD (bh_device.hpp): neighbouring
-// waves walk nearly the same nodes, so a run shares its XCD's L2 (C3 -1.5 % at runs of 32..512
-// against the round-robin default).
-#ifndef BH_TRAV_XCD_RUN
-#define BH_TRAV_XCD_RUN 64
-#endif
-constexpr int TB = 64;  // one wave per workgroup: finest dispatch granularity (C4 -1.5 %, C3 -0.5 %)
-// Waves per workgroup of k_traverse: up to MAX_WPB, chosen per launch (waves_per_group below).
-// A workgroup's waves share one CU and its scalar data cache, and neighbouring waves walk nearly
-// the same node records.
-constexpr int MAX_WPB = 8;
-static_assert(BH_TRAV_XCD_RUN % MAX_WPB == 0, "an XCD run holds whole workgroups");
-// Workgroups of one remapped group (8 XCDs x one run each) and the whole groups of a grid: the
-// tail past them keeps its dispatch order (k_traverse, bh_launch_plan).
-__host__ __device__ constexpr uint32_t xcd_group_blocks(uint32_t wpb) {
-    return 8u * (BH_TRAV_XCD_RUN / wpb);
-}
-__host__ __device__ constexpr uint32_t xcd_full_groups(uint32_t groups, uint32_t wpb) {
-    return groups / xcd_group_blocks(wpb);
-}
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x8 __attribute__((ext_vector_type(8)));
-
-// Node record through an explicit scalar load whose wait is placed by hand (nwait): the next
-// record is requested as soon as the cursor decision is made and waited for only after the
-// point-force block, so its latency hides behind that block's fp64 work.  (The compiler would
-// sink a plain load below the block, to its first use.)
-__device__ __forceinline__ u32x8 nload(const Node *p) {
-    u32x8 v;
-    asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(v) : "s"(p) : "memory");
-    return v;
-}
-// Same, addressed as base + 32-bit byte offset (s_load's SGPR offset): one shift per
-// iteration instead of a 64-bit address computation.  Only for node arrays below 4 GiB.
-__device__ __forceinline__ u32x8 nload_off(const Node *base, uint32_t idx) {
-    u32x8 v;
-    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(v) : "s"(base), "s"(idx << 5) : "memory");
-    return v;
-}
-__device__ __forceinline__ void nwait(u32x8 &v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(v)); }
-__device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
-    return __longlong_as_double((long long)(((uint64_t)hi << 32) | lo));
-}
 
 // Which lanes are active at a stop (cur >= the lane's resume point): a per-lane compare at every
 // stop and a per-lane `resume = next` in every point-force block.  The alternative (round 6) kept
@@ -80,7 +36,7 @@ __device__ __forceinline__ double as_f64(uint32_t lo, uint32_t hi) {
 // loses.  That walk is in the history at 3db5b68.
 // POT (the step log's kick-only walk, engine.cpp step_log_step): the walk also sums the body's
 // potential over the nodes it takes, s += mass * invR with the block's own invR -- the term and
-// the order of potential.hip's pot_walk, so -(G * s) is bh_compute_potential's phi on this tree.
+// the order of probe_walk's (cursor_walk.hpp), so -(G * s) is bh_compute_potential's phi on this tree.
 // Unlike the force's, the own leaf's term m / sqrt(soft2) is no +-0: it is left out by identity
 // (the exact walk never takes the own leaf; the fast walk does, for its +-0 force).  s is never
 // -0.0 (potential.hip), so a massless node's +-0 term on the fast path leaves it unchanged.
@@ -90,27 +46,14 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
                                      double s2root, double thr0, uint32_t self, uint32_t resume,
                                      double &fx, double &fy, uint32_t &nvis, uint32_t &niters,
                                      uint32_t &ncontrib, uint32_t &nblocks, double &pot) {
-    uint32_t cur = 0;
-    // one iteration on record `rec`; the next record is requested into `nrec`.  The loop body
-    // is unrolled twice with the two records swapping roles (no SGPR copies per iteration).
-    // Loading node T (past the last one) is harmless: the node array has slack beyond T.
-    auto iter = [&](const u32x8 &rec, u32x8 &nrec) __attribute__((always_inline)) {
-        const double comX = as_f64(rec[0], rec[1]), comY = as_f64(rec[2], rec[3]);
-        const double mass = as_f64(rec[4], rec[5]);
-        uint32_t meta = rec[7];
-        asm volatile("" : "+s"(meta));  // keep the flag tests scalar (s_bitcmp)
-        uint32_t next = rec[6];
-        next = next > cur ? next : cur + 1;  // structural guard: the cursor always advances
-        // mass == 0.0 (BHA:216): not visited.  The fast path needs no test: a massless leaf's
-        // term is an exact +-0 (mass 0, finite f), and a massless internal node carries the leaf
-        // flag too (bh_device.hpp NODE_SKIP), so the wave never descends below it -- only the
-        // visit-counting variant must skip it.
-        if ((!FAST || COUNT) && (meta & NODE_SKIP)) {
-            cur = next;
-            nrec = OFF32 ? nload_off(nodes, cur) : nload(nodes + cur);
-            nwait(nrec);
-            return;
-        }
+    // mass == 0.0 (BHA:216): not visited.  The fast path needs no test: a massless leaf's
+    // term is an exact +-0 (mass 0, finite f), and a massless internal node carries the leaf
+    // flag too (bh_device.hpp NODE_SKIP), so the wave never descends below it -- only the
+    // visit-counting variant must skip it.
+    cursor_walk<OFF32, !FAST || COUNT>(nodes, T, [&](const CursorStop<OFF32> &st)
+                                                     __attribute__((always_inline)) {
+        const double comX = st.comX, comY = st.comY, mass = st.mass;
+        const uint32_t meta = st.meta, next = st.next, cur = st.cur;
         // lane masks in SGPRs straight from the compares; per-lane booleans via inverse ballot
         const uint64_t act_m = __builtin_amdgcn_ballot_w64(cur >= resume);
         if (COUNT) {
@@ -154,7 +97,7 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
             open_m = act_m & ~acc_m;
         }
         const uint32_t ncur = open_m != 0ull ? cur + 1 : next;  // descend iff some lane opened
-        nrec = OFF32 ? nload_off(nodes, ncur) : nload(nodes + ncur);
+        st.fetch(ncur);
         if (COUNT) {  // contributions in the reference's sense: the own leaf is not one
             const bool own = (meta & NODE_LEAF) && (meta & NODE_BODY_MASK) == self;
             ncontrib += (__builtin_amdgcn_inverse_ballot_w64(contrib_m) && !own) ? 1u : 0u;
@@ -181,20 +124,8 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
             }
             resume = next;
         }
-        nwait(nrec);
-        cur = ncur;
-    };
-    if (T == 0) return;  // no body inside the root cell: an empty tree
-    u32x8 r0 = nload(nodes), r1;
-    nwait(r0);
-    // (a `while (cur < T)` head with one exit test in the middle made the compiler keep a dead
-    // v_readfirstlane per two stops)
-    while (true) {
-        iter(r0, r1);
-        if (cur >= T) break;
-        iter(r1, r0);
-        if (cur >= T) break;
-    }
+        return ncur;
+    });
 }
 
 
@@ -612,14 +543,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_traverse(const Node *__restric
 #else
     const uint64_t t_start = wo.cost ? wall_clock64() : 0;
 #endif
-    // xcd_block() with runs of BH_TRAV_XCD_RUN / wpb workgroups (= BH_TRAV_XCD_RUN waves)
-    uint32_t b = blockIdx.x;
-    {
-        const uint32_t C = BH_TRAV_XCD_RUN / wpb, G = xcd_group_blocks(wpb);
-        const uint32_t full = xcd_full_groups(gridDim.x, wpb);
-        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
-    }
-    uint32_t v = b * wpb + (threadIdx.x >> 6);
+    uint32_t v = xcd_run_wave(wpb);
     if (wo.order)  // the v-th run to start is the order[v]-th run of waves (wave_order)
         v = wo.order[v / BH_TRAV_XCD_RUN] * BH_TRAV_XCD_RUN + v % BH_TRAV_XCD_RUN;
     trav_wave<COUNT, OFF32, KICK, BFS>(v, bpw, t_start, nodes, d_T, x, y, m, cidx, lo, hi, fp, g,
@@ -640,13 +564,7 @@ __global__ __launch_bounds__(TB * MAX_WPB) void k_traverse_pot(
 #else
     const uint64_t t_start = wo.cost ? wall_clock64() : 0;
 #endif
-    uint32_t b = blockIdx.x;  // (k_traverse's remap)
-    {
-        const uint32_t C = BH_TRAV_XCD_RUN / wpb, G = xcd_group_blocks(wpb);
-        const uint32_t full = xcd_full_groups(gridDim.x, wpb);
-        if (b < full * G) b = (b / 8 / C) * G + (b % 8) * C + (b / 8) % C;
-    }
-    uint32_t v = b * wpb + (threadIdx.x >> 6);
+    uint32_t v = xcd_run_wave(wpb);
     if (wo.order) v = wo.order[v / BH_TRAV_XCD_RUN] * BH_TRAV_XCD_RUN + v % BH_TRAV_XCD_RUN;
     trav_wave<false, OFF32, KICK_ONLY, false, true>(
         v, bpw, t_start, nodes, d_T, x, y, m, cidx, lo, hi, fp, g, a2,
@@ -845,6 +763,15 @@ uint32_t waves_per_group(uint32_t waves, uint32_t bpw) {
     return waves >= BH_TRAV_WPB_FULL_WAVES ? 4u : waves >= 1024 ? 8u : 1u;
 }
 
+WalkShape walk_shape(int64_t lanes, bool full_waves) {
+    WalkShape w;
+    w.bpw = full_waves ? (uint32_t)TB : bodies_per_wave(lanes);
+    w.waves = (uint32_t)((lanes + w.bpw - 1) / w.bpw);
+    w.wpb = waves_per_group(w.waves, w.bpw);
+    w.grid = (w.waves + w.wpb - 1) / w.wpb;
+    return w;
+}
+
 // Breadth-first walks (bfs_walk, one body per wave) for launches of up to BH_TRAV_BFS_MAX bodies
 // (0: never).  Measured (profiles/r06z2_*): C1 'R' (2 000 bodies) traversal
 // 67.5 -> 39.8 us; C1 code default (12 500) 102 -> 135 us -- 12 500 one-body waves are ~3
@@ -871,8 +798,7 @@ static int64_t bfs_max_bodies(int kick_mode) {
 bool traverse_is_bfs(size_t node_cap, int64_t lo, int64_t hi, int kick_mode, bool counting,
                      bool pot) {
     if (pot) return false;  // (the step log's walk is the cursor walk: bfs_walk has no potential)
-    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
-    return !counting && off32 && lo == 0 && hi > 0 && hi <= bfs_max_bodies(kick_mode) &&
+    return !counting && node_off32(node_cap) && lo == 0 && hi > 0 && hi <= bfs_max_bodies(kick_mode) &&
            kick_mode != KICK_OWN_DRIFT && kick_mode != KICK_OWN_ONLY;
 }
 
@@ -906,8 +832,7 @@ void traverse(const Node *nodes, size_t node_cap, const uint32_t *d_T, double *x
               hipStream_t s, const KickArgs *kick, const uint32_t *lanes, const WaveOrder *wo,
               double *phi) {
     if (hi <= lo) return;
-    // node records addressed by a 32-bit byte offset while the array stays below 4 GiB
-    const bool off32 = node_cap * sizeof(Node) < (size_t(1) << 32);
+    const bool off32 = node_off32(node_cap);
     const TraverseShape t = traverse_shape(node_cap, lo, hi, kick ? kick->mode : KICK_NONE,
                                            cnt != nullptr, wo && wo->order, phi != nullptr);
     const bool bfs = t.bfs;
