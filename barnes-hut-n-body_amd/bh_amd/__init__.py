@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = (
     "bh_launch_plan", "bh_render_quads", "bh_render_quads_kernel_ms",
     "bh_compute_field", "bh_field_kernel_ms",
     "bh_find_neighbors", "bh_neighbors_kernel_ms", "bh_neighbor_reach",
+    "bh_find_knn", "bh_find_knn_bodies", "bh_knn_kernel_ms", "bh_knn_shape",
     "bh_find_groups", "bh_groups_kernel_ms",
     "bh_compute_field_direct", "bh_compute_force_error", "bh_direct_field_kernel_ms",
     "bh_direct_field_shape",
@@ -324,6 +325,12 @@ def load_library(path: str | None = None):
                                       _I64P, _D, _I64P, _I64P, ctypes.c_int64, _I64P]
     lib.bh_neighbors_kernel_ms.argtypes = [_VP, _D]
     lib.bh_neighbor_reach.argtypes = [ctypes.POINTER(BhParams), ctypes.c_int32, _D]
+    lib.bh_find_knn.argtypes = [_VP, ctypes.c_int64, _D, _D, ctypes.c_int32, ctypes.c_double,
+                                _I64P, _D, _I64P]
+    lib.bh_find_knn_bodies.argtypes = [_VP, ctypes.c_int32, ctypes.c_double, _I64P, _D, _I64P,
+                                       ctypes.c_int64, _I64P]
+    lib.bh_knn_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_knn_shape.argtypes = [ctypes.c_int64, ctypes.c_int32, _I64P]
     lib.bh_find_groups.argtypes = [_VP, ctypes.c_double, ctypes.c_int64, _I64P, ctypes.c_int64,
                                    _I64P, ctypes.c_int64, ctypes.POINTER(BhGroup),
                                    ctypes.c_int64, ctypes.POINTER(BhGroupsSummary)]
@@ -488,6 +495,17 @@ def direct_field_shape(n: int):
     if rc != BH_OK:
         raise BhError(rc, "bh_direct_field_shape: invalid arguments")
     return int(out[0]), int(out[1]), int(out[2])
+
+
+def knn_shape(n: int, k: int):
+    """(lanes per wave, waves per workgroup, LDS bytes per workgroup, workgroups) of the
+    k-nearest walk behind find_knn and find_knn_bodies for `n` probes and lists of `k` entries
+    (bh_knn_shape; host-only, no device)."""
+    out = np.zeros(4, dtype=np.int64)
+    rc = load_library().bh_knn_shape(int(n), int(k), out.ctypes.data_as(_I64P))
+    if rc != BH_OK:
+        raise BhError(rc, "bh_knn_shape: invalid arguments")
+    return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
 
 def tracer_launch_shape(n: int):
@@ -931,6 +949,56 @@ class Engine:
         """HIP-event time (ms) of the last find_neighbors call's device work, first walk to
         last kernel (bh_neighbors_kernel_ms)."""
         return self._kernel_ms(self._lib.bh_neighbors_kernel_ms)
+
+    def find_knn(self, px, py, k, r_max=float("inf")):
+        """bh_find_knn: the k nearest bodies of the probe points (px, py), no farther than r_max.
+        Returns (idx[n, k], d2[n, k], found[n]): row j holds the indices into get_bodies() after
+        the call and the squared distances of probe j's nearest, ascending under (d2, index);
+        found[j] is the number of entries, the tail of a shorter row holds -1 and +inf.  The
+        candidates are the bodies in the tree of non-zero mass with dx*dx + dy*dy <= r_max*r_max;
+        a probe on a body finds it with d2 = 0.  A build, exactly as compute_field (the jitter may
+        move positions); the probes never enter the state."""
+        px = np.ascontiguousarray(px, dtype=np.float64)
+        py = np.ascontiguousarray(py, dtype=np.float64)
+        n = len(px)
+        if px.ndim != 1 or py.shape != px.shape:
+            raise ValueError("px and py must be 1-d arrays of equal length")
+        kk = max(int(k), 0)
+        idx = np.empty((n, kk), dtype=np.int64)
+        d2 = np.empty((n, kk), dtype=np.float64)
+        found = np.empty(n, dtype=np.int64)
+        self._check(self._lib.bh_find_knn(self._h, n, _dp(px), _dp(py), int(k), float(r_max),
+                                          idx.ctypes.data_as(_I64P), _dp(d2),
+                                          found.ctypes.data_as(_I64P)))
+        return idx, d2, found
+
+    def find_knn_bodies(self, k, r_max=float("inf")):
+        """bh_find_knn_bodies: find_knn with the bodies themselves as the probes -- row i belongs
+        to body i of get_bodies() after the call and holds its k nearest *other* bodies (a
+        coincident other body is found with d2 = 0).  Nothing is uploaded.  Returns
+        (idx[N, k], d2[N, k], found[N])."""
+        kk = max(int(k), 0)
+        cap = self.num_bodies()
+        rows = ctypes.c_int64(0)
+        for _ in range(2):
+            idx = np.empty((cap, kk), dtype=np.int64)
+            d2 = np.empty((cap, kk), dtype=np.float64)
+            found = np.empty(cap, dtype=np.int64)
+            rc = self._lib.bh_find_knn_bodies(self._h, int(k), float(r_max),
+                                              idx.ctypes.data_as(_I64P), _dp(d2),
+                                              found.ctypes.data_as(_I64P), cap,
+                                              ctypes.byref(rows))
+            if rc != BH_E_CAPACITY:
+                break
+            cap = rows.value
+        self._check(rc)
+        n = rows.value
+        return idx[:n], d2[:n], found[:n]
+
+    def knn_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last find_knn / find_knn_bodies call's device work, seed
+        kernel to last store (bh_knn_kernel_ms)."""
+        return self._kernel_ms(self._lib.bh_knn_kernel_ms)
 
     def find_groups(self, link, min_members=1, labels=True, members=False):
         """bh_find_groups: the friends-of-friends groups of the bodies at linking length `link`.
@@ -1483,6 +1551,18 @@ class PhysicsEngine:
         _, nearest, _ = self._eng.find_neighbors([float(x)], [float(y)], float(r), counts=False)
         self._pull()
         return self._bodies[int(nearest[0])] if nearest[0] >= 0 else None
+
+    def nearest(self, x, y, k, r_max=float("inf")):
+        """The up to k Body objects of the caller's list nearest to (x, y) and no farther than
+        r_max, nearest first, ties to the lower list index (Engine.find_knn: among the bodies in
+        the tree of non-zero mass).  Builds a tree as step()'s first half does, so its jitter is
+        written back into the Body objects."""
+        self._eng.set_params(self._params())
+        if self._changed():
+            self._push()
+        idx, _, found = self._eng.find_knn([float(x)], [float(y)], int(k), float(r_max))
+        self._pull()
+        return [self._bodies[int(c)] for c in idx[0, :int(found[0])]]
 
     def groups(self, link, min_members=2):
         """The friends-of-friends groups of the caller's list at linking length `link`

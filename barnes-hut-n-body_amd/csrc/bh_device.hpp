@@ -823,6 +823,29 @@ hipError_t neighbors_sort(int64_t total, int64_t n, const int64_t *offsets, uint
                           uint32_t *idx_s, int bits, int64_t *out, void *scratch,
                           size_t &scratch_bytes, hipStream_t s);
 
+// ---- launchers (knn.hip): the k nearest bodies of probe points and of the bodies ----------
+// What knn_walk launches for `lanes` lanes and lists of k entries (host-only; knn_walk itself
+// launches from it, and bh_knn_shape reports it): walk_shape's lanes per wave and waves, its waves
+// per workgroup halved until the workgroup's lists -- wpb x 64 x k entries of 12 bytes in LDS --
+// fit 64 KiB.
+struct KnnShape {
+    uint32_t bpw, waves, wpb, grid;
+    uint32_t lds;  // bytes of LDS per workgroup
+};
+KnnShape knn_shape(int64_t lanes, int k);
+// The candidate set and the exact test are neighbors_count's, with the one radius r_max (>= 0,
+// +inf: no cap).  Lane q < n is a probe: with self, the body in slot q at (px[q], py[q]) -- the
+// state's planes --, whose own leaf is no candidate and whose row is map[q] = cidx[q]; else probe
+// map[q] = order[q] of the caller's list at (px[map[q]], py[map[q]]).  Row j = the first
+// min(k, candidates) candidates under (d2, caller index): idx[j k + i], d2[j k + i] ascending,
+// the tail -1 and +inf; found[j] the number of entries (each plane nullable).  seed: n doubles of
+// scratch (every lane's starting radius^2, from the leaf sequence).  d_T and d_count null: no tree.
+void knn_walk(const Node *nodes, size_t node_cap, const uint32_t *d_T, const uint32_t *cidx,
+              const LeafList &leaves, const uint32_t *d_count, const uint32_t *map,
+              const double *px, const double *py, bool self, int64_t n, int k, double r_max,
+              const Geometry &g, const NeighborReach &rc, double *seed, int64_t *idx, double *d2,
+              int64_t *found, hipStream_t s);
+
 // ---- launchers (groups.hip): friends-of-friends groups of the leaf sequence ---------------
 // The working set of bh_find_groups for a list of n bodies (the engine allocates it).  The
 // union-find and the leaf planes are indexed by body slot or by leaf (n entries); the scans'

@@ -276,6 +276,21 @@ struct bh_engine {
     void *nbr_sort = nullptr;      // the segmented sort's scratch
     size_t nbr_sort_bytes = 0;
     Stopwatch nbr_sw;  // from the first walk to the last kernel of the last call
+    // bh_find_knn / bh_find_knn_bodies (knn.hip): the calls' own buffers, allocated on first use
+    // and grown when needed -- per uploaded probe (knn_cap), per lane (knn_lane_cap) and per row
+    // entry (knn_row_cap)
+    double *knn_in = nullptr;      // px, py planes of knn_cap probes
+    uint32_t *knn_u32 = nullptr;   // key, sorted key, index, order planes
+    void *knn_scratch = nullptr;   // the probes' sort
+    size_t knn_scratch_bytes = 0;
+    int64_t knn_cap = 0;
+    double *knn_seed = nullptr;    // every lane's starting radius^2
+    int64_t *knn_found = nullptr;
+    int64_t knn_lane_cap = 0;
+    int64_t *knn_idx = nullptr;    // the rows: k entries per lane
+    double *knn_d2 = nullptr;
+    int64_t knn_row_cap = 0;
+    Stopwatch knn_sw;  // from the seed kernel to the walk's last store
     // bh_find_groups (groups.hip): the call's own buffers, allocated on first use and grown when
     // the list outgrows them (grp_cap bodies)
     uint32_t *grp_u32 = nullptr;   // parent, minc, rootof, val, val_s; flag, gid, first, keep, kidx
@@ -1961,6 +1976,69 @@ int neighbors_launch(bh_engine *e, NeighborQuery &q, bool tree) {
     }
     q.filled = q.lists && q.total <= q.cap;
     return e->nbr_sw.stop(e, e->stream);
+}
+
+// The caller's arguments of bh_find_knn (host arrays) or bh_find_knn_bodies (self: the probes are
+// the bodies of the state, nothing is uploaded), and which result planes are wanted.
+struct KnnQuery {
+    int64_t n;  // probes (self: filled in by the launch, e->n)
+    const double *px, *py;
+    int k;
+    double r_max;
+    bool self;
+    bool want_idx, want_d2, want_found;
+};
+
+// bh_find_knn / bh_find_knn_bodies: the leaf sequence, then -- for a probe list -- upload, key and
+// sort as bh_compute_field does, then the seed kernel and the walk into the engine's own planes.
+// The bodies are their own probes in slot order, which a full build left in Morton order.
+int knn_launch(bh_engine *e, KnnQuery &q, bool tree) {
+    if (q.self) q.n = e->n;
+    const int64_t P = q.n;
+    if (P <= 0) return BH_OK;
+    if (tree) TRY(build_leaf_list(e));
+    const double *px = e->st.x, *py = e->st.y;
+    const uint32_t *map = e->st.cidx;
+    if (!q.self) {
+        if (outgrown(e->knn_cap, e->knn_in, P)) {
+            const size_t cap = (size_t)P;
+            TRY(dev_alloc(e, e->knn_in, 2 * cap));   // px, py
+            TRY(dev_alloc(e, e->knn_u32, 4 * cap));  // key, sorted key, index, order
+            if (e->knn_scratch) (void)hipFree(e->knn_scratch);
+            e->knn_scratch = nullptr;
+            e->knn_scratch_bytes = field_sort_bytes(P);
+            HIPCHK(e, hipMalloc(&e->knn_scratch, e->knn_scratch_bytes ? e->knn_scratch_bytes : 1));
+            e->knn_cap = P;
+        }
+        const size_t cap = (size_t)e->knn_cap;
+        double *dx = e->knn_in, *dy = dx + cap;
+        TRY(upload_probes(e, Probes{P, q.px, q.py, nullptr}, dx, dy, nullptr));
+        uint32_t *key = e->knn_u32, *key_s = key + cap, *idx = key_s + cap, *order = idx + cap;
+        HIPCHK(e, field_order(P, dx, dy, e->geo, key, key_s, idx, order, e->knn_scratch,
+                              e->knn_scratch_bytes, e->stream));
+        px = dx;
+        py = dy;
+        map = order;
+    }
+    if (outgrown(e->knn_lane_cap, e->knn_seed, P)) {
+        TRY(dev_alloc(e, e->knn_seed, (size_t)P));
+        TRY(dev_alloc(e, e->knn_found, (size_t)P));
+        e->knn_lane_cap = P;
+    }
+    const int64_t rows = P * q.k;
+    if (outgrown(e->knn_row_cap, e->knn_idx, rows)) {
+        TRY(dev_alloc(e, e->knn_idx, (size_t)rows));
+        TRY(dev_alloc(e, e->knn_d2, (size_t)rows));
+        e->knn_row_cap = rows;
+    }
+    TRY(e->knn_sw.start(e, e->stream));
+    knn_walk(tree ? e->nodes : nullptr, tree ? e->node_cap : 0, tree ? e->base + e->n : nullptr,
+             tree ? e->st.cidx : nullptr, tree ? e->leaves : LeafList{nullptr},
+             tree ? e->leaf_count : nullptr, map, px, py, q.self, P, q.k, q.r_max, e->geo,
+             neighbor_reach_terms(e->geo), e->knn_seed, q.want_idx ? e->knn_idx : nullptr,
+             q.want_d2 ? e->knn_d2 : nullptr, q.want_found ? e->knn_found : nullptr, e->stream);
+    HIPCHK(e, hipGetLastError());
+    return e->knn_sw.stop(e, e->stream);
 }
 
 // The planes of bh_find_groups' buffers for the engine's grp_cap.
@@ -3740,13 +3818,14 @@ void bh_destroy(bh_engine *e) {
                     e->qd_out, e->qd_count, e->fld_in, e->fld_out, e->fld_u32, e->fld_scratch,
                     e->dfl_in, e->dfl_out, e->dfl_u32, e->dfl_slot_of, e->fgr_out, e->fgr_stats,
                     e->nbr_in, e->nbr_u32, e->nbr_i64, e->nbr_d2, e->nbr_scratch, e->nbr_idx,
-                    e->nbr_list, e->nbr_sort,
+                    e->nbr_list, e->nbr_sort, e->knn_in, e->knn_u32, e->knn_scratch, e->knn_seed,
+                    e->knn_found, e->knn_idx, e->knn_d2,
                     e->grp_u32, e->grp_u64, e->grp_i64, e->grp_part, e->grp_groups, e->grp_scratch,
                     e->trc, e->trc_snap, e->trc_u32, e->trc_scratch, e->slog_ring, e->slog_phi,
                     e->slog_stage, e->slog_part, e->slog_keep, e->slog_pos, e->slog_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
-    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->nbr_sw, &e->grp_sw,
+    for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->nbr_sw, &e->knn_sw, &e->grp_sw,
                           &e->grp_sw_run, &e->rnd_sw, &e->qd_sw})
         sw->destroy();
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
@@ -4474,6 +4553,96 @@ int bh_find_neighbors(bh_engine *e, int64_t n_probe, const double *px, const dou
 
 int bh_neighbors_kernel_ms(const bh_engine *e, double *ms) {
     return kernel_ms(e, &bh_engine::nbr_sw, ms);
+}
+
+// null if (k, r_max) are usable and n lists of k entries can be addressed, else what is wrong
+static const char *knn_args_error(int64_t n, int32_t k, double r_max) {
+    if (k < 1 || k > BH_KNN_MAX_K) return "k must be in 1..64";
+    if (!(r_max >= 0.0)) return "r_max must be >= 0";
+    if (n * (int64_t)k > (int64_t)INT32_MAX) return "more than 2^31 - 1 entries in all: ask in batches";
+    return nullptr;
+}
+
+// The rows of the first n lanes of m's planes to the caller's arrays (each nullable).
+static int knn_copy_out(bh_engine *m, int64_t n, int k, int64_t *idx, double *d2, int64_t *found) {
+    const size_t rows = (size_t)n * (size_t)k;
+    if (idx && rows)
+        HIPCHK(m, hipMemcpy(idx, m->knn_idx, sizeof(int64_t) * rows, hipMemcpyDeviceToHost));
+    if (d2 && rows)
+        HIPCHK(m, hipMemcpy(d2, m->knn_d2, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    if (found && n)
+        HIPCHK(m, hipMemcpy(found, m->knn_found, sizeof(int64_t) * (size_t)n,
+                            hipMemcpyDeviceToHost));
+    return BH_OK;
+}
+
+int bh_find_knn(bh_engine *e, int64_t n_probe, const double *px, const double *py, int32_t k,
+                double r_max, int64_t *idx, double *d2, int64_t *found) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    TRY(check_list(e, "bh_find_knn", "n_probe", n_probe, px && py, "px or py"));
+    if (const char *bad = knn_args_error(n_probe, k, r_max)) {
+        e->err = std::string("bh_find_knn: ") + bad;
+        return BH_E_INVALID;
+    }
+    KnnQuery q{n_probe, px, py, (int)k, r_max, false, idx != nullptr, d2 != nullptr,
+               found != nullptr};
+    return query_call(e, [&](bh_engine *m, bool run) {
+        if (q.n == 0) run = false;
+        TRY(field_rank(m, run, [&](bool tree) { return knn_launch(m, q, tree); }));
+        return run ? knn_copy_out(m, q.n, q.k, idx, d2, found) : BH_OK;
+    });
+}
+
+int bh_find_knn_bodies(bh_engine *e, int32_t k, double r_max, int64_t *idx, double *d2,
+                       int64_t *found, int64_t rows_cap, int64_t *n_rows) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    const char *bad = knn_args_error(0, k, r_max);
+    if (!bad && rows_cap < 0) bad = "rows_cap must be >= 0";
+    if (bad) {
+        e->err = std::string("bh_find_knn_bodies: ") + bad;
+        return BH_E_INVALID;
+    }
+    int64_t N = 0;
+    const char *refused = nullptr;  // why the walk was not launched
+    TRY(query_call(e, [&](bh_engine *m, bool run) {
+        KnnQuery q{0, nullptr, nullptr, (int)k, r_max, true, idx != nullptr, d2 != nullptr,
+                   found != nullptr};
+        TRY(field_rank(m, run, [&](bool tree) {
+            N = m->n;
+            if (N > rows_cap) return BH_OK;
+            if ((refused = knn_args_error(N, k, r_max))) return BH_OK;
+            return knn_launch(m, q, tree);
+        }));
+        if (!run || N > rows_cap || refused) return BH_OK;
+        return knn_copy_out(m, N, q.k, idx, d2, found);
+    }));
+    if (n_rows) *n_rows = N;
+    if (refused) {
+        e->err = std::string("bh_find_knn_bodies: ") + refused;
+        return BH_E_INVALID;
+    }
+    if (N > rows_cap) {
+        e->err = "bh_find_knn_bodies: rows_cap is below the number of bodies; *n_rows holds it";
+        return BH_E_CAPACITY;
+    }
+    return BH_OK;
+}
+
+int bh_knn_kernel_ms(const bh_engine *e, double *ms) {
+    return kernel_ms(e, &bh_engine::knn_sw, ms);
+}
+
+int bh_knn_shape(int64_t n_lane, int32_t k, int64_t *out4) {
+    if (!out4 || n_lane < 0 || n_lane > ((int64_t)1 << 28) || k < 1 || k > BH_KNN_MAX_K)
+        return BH_E_INVALID;
+    const KnnShape sh = knn_shape(n_lane, k);
+    out4[0] = sh.bpw;
+    out4[1] = sh.wpb;
+    out4[2] = sh.lds;
+    out4[3] = sh.grid;
+    return BH_OK;
 }
 
 int bh_find_groups(bh_engine *e, double link, int64_t min_members, int64_t *label,

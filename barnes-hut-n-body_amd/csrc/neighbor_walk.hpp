@@ -1,5 +1,6 @@
 // The radius walk over the flattened quadtree, shared by its two users: bh_find_neighbors
-// (neighbors.hip: one lane = one probe) and bh_find_groups (groups.hip: one lane = one leaf).
+// (neighbors.hip: one lane = one probe), bh_find_groups (groups.hip: one lane = one leaf) and
+// bh_find_knn (knn.hip: one lane = one probe with a list of its k best).
 // Device code only; every name is local to the including file.
 //
 // The walk is a stop of cursor_walk.hpp's cursor_walk: one wave-shared pre-order cursor, the node
@@ -25,7 +26,17 @@ constexpr uint32_t NBR_NONE = 0xFFFFFFFFu;  // no neighbour yet: above every cal
 // d2 so far -- a body farther than the best cannot become the smallest, one at the same d2 still
 // can (by index), and `<=` keeps it.  NBR_FILL: the caller indices into the lane's segment.
 // NBR_LINK: nothing is kept; the lane's `link` functor is called with the hit leaf's body slot.
-enum NbrMode { NBR_COUNT = 0, NBR_NEAREST = 1, NBR_PICK = 2, NBR_FILL = 3, NBR_LINK = 4 };
+// NBR_KNN: the lane's `link` functor is its list of the k best (knn.hip KnnHeap): the leaf of body
+// slot link.self is no hit, a hit goes to link.insert(L, d2, caller index), and insert shrinks
+// the lane's radius to the k-th best once the list is full -- NBR_PICK's rule for any k.
+enum NbrMode {
+    NBR_COUNT = 0,
+    NBR_NEAREST = 1,
+    NBR_PICK = 2,
+    NBR_FILL = 3,
+    NBR_LINK = 4,
+    NBR_KNN = 5
+};
 
 struct NbrLane {
     double bx, by;    // the probe
@@ -58,11 +69,15 @@ __device__ __forceinline__ void nbr_walk_wave(const Node *__restrict__ nodes, ui
         const double dy = st.comY - L.by;
         const double d2 = dx * dx + dy * dy;
         if (meta & NODE_LEAF) {  // the record is the body: the exact test
-            const bool hit = active && d2 <= L.r2;
+            bool hit = active && d2 <= L.r2;
+            if constexpr (MODE == NBR_KNN) hit = hit && (meta & NODE_BODY_MASK) != link.self;
             const uint64_t hit_m = __builtin_amdgcn_ballot_w64(hit);
             st.fetch(next);
             if (hit_m != 0ull) {
-                if (MODE == NBR_LINK) {
+                if constexpr (MODE == NBR_KNN) {
+                    const uint32_t c = cidx[meta & NODE_BODY_MASK];  // wave-uniform address
+                    if (hit) link.insert(L, d2, c);
+                } else if (MODE == NBR_LINK) {
                     if (hit) link(meta & NODE_BODY_MASK);
                 } else {
                     uint32_t c = 0;

@@ -301,6 +301,19 @@ Body *PhysicsEngine::pick(double x, double y, double r) {
     return nearest >= 0 ? &(*bodies_)[(size_t)nearest] : nullptr;
 }
 
+std::vector<Body *> PhysicsEngine::nearest(double x, double y, int32_t k, double rMax) {
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    std::vector<int64_t> idx((size_t)(k > 0 ? k : 0), -1);
+    int64_t found = 0;
+    check(bh_find_knn(eng_, 1, &x, &y, k, rMax, idx.data(), nullptr, &found));
+    pullBodies(false);  // its buildTree can jitter positions (BHA:146-151)
+    std::vector<Body *> out;
+    out.reserve((size_t)found);
+    for (int64_t i = 0; i < found; ++i) out.push_back(&(*bodies_)[(size_t)idx[(size_t)i]]);
+    return out;
+}
+
 std::vector<std::vector<Body *>> PhysicsEngine::groups(double link, int64_t minMembers) {
     pushParams();
     if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits

@@ -114,6 +114,13 @@ public:
     // does -- its jitter is written back into the list; the pointer is into that list.
     Body *pick(double x, double y, double r);
 
+    // The up to k bodies of the caller's list nearest to (x, y) and no farther than rMax, nearest
+    // first, ties to the lower list index (bh_find_knn with one probe; no reference counterpart):
+    // among the bodies in the tree of non-zero mass; k in 1..64, rMax = +inf for no cap.  Builds
+    // a tree as step()'s first half does -- its jitter is written back into the list; the
+    // pointers are into that list.
+    std::vector<Body *> nearest(double x, double y, int32_t k, double rMax);
+
     // The friends-of-friends groups of the caller's list at linking length `link`
     // (bh_find_groups; no reference counterpart): one list of bodies per group of at least
     // minMembers members, in catalogue order (ascending lowest list index; within a group

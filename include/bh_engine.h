@@ -200,7 +200,8 @@ int bh_step(bh_engine *e, int32_t k);
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
  * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
- * bh_find_neighbors, bh_find_groups, bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
+ * bh_find_neighbors, bh_find_knn, bh_find_knn_bodies, bh_find_groups,
+ * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers, and
  * bh_set_step_log, bh_get_step_log and bh_get_step_log_phi.
@@ -389,6 +390,66 @@ int bh_neighbors_kernel_ms(const bh_engine *e, double *ms);
  * of mass's rounding, all with a relative margin of 2^-40.
  * BH_E_INVALID: p or reach NULL, depth outside 0..39, params without a valid root cell. */
 int bh_neighbor_reach(const bh_params *p, int32_t depth, double *reach);
+
+/* The k nearest bodies of n_probe points (bh_find_knn) and of every body of the state
+ * (bh_find_knn_bodies): bounded work per probe wherever it lies, where a fixed radius drowns in a
+ * dense core and finds nothing in the tails.
+ * The tree, the state semantics, the errors and the multi-device handle are exactly
+ * bh_find_neighbors': the build with its jitter or the carried tree, always a full build, never
+ * sharded; a tree-flag error is returned the same way; the call leaves what
+ * bh_compute_accelerations would leave; on a multi-device handle every member builds and member 0
+ * answers.
+ * The candidate set S is bh_find_neighbors': every non-empty leaf under no mass-0 node.  Body b of
+ * S is a candidate of probe j iff
+ *     r_max >= 0 && dx*dx + dy*dy <= r_max*r_max,   dx = x_b - px[j];  dy = y_b - py[j]
+ * in binary64, nothing fused, on the positions of the state after the call's build.  r_max = +inf
+ * means no cap.  A NaN probe coordinate finds nothing; probes outside the root cell, at 2^40 or at
+ * 1e300 are legal, and a d2 of +inf is a value like any other.  bh_find_knn skips nothing by
+ * identity: a probe on a body finds it with d2 = 0.
+ * Row j is the first min(k, candidates) candidates under the total order (d2, caller index):
+ *   idx[j*k + i]   the caller index of the i-th nearest,
+ *   d2[j*k + i]    and its d2 = dx*dx + dy*dy, in that order;
+ *   found[j]       the number of entries; the tail of a shorter row holds -1 and +inf.
+ * idx, d2 [n_probe * k] and found [n_probe] are each nullable.  Caller indices are indices into
+ * the list bh_get_bodies returns after the call.  The row equals bh_find_neighbors' list for
+ * r = r_max, sorted by (d2, index) and cut at k.
+ * Every output is an integer or a d2 that one candidate's arithmetic produced -- no
+ * floating-point sum, no atomic on a float: two calls, two engines holding the same list, or a
+ * multi-device handle return identical bytes.  The walk prunes by bh_neighbor_reach's bound
+ * around a radius that starts from a seed (an upper bound on the k-th distance taken from k real
+ * candidates) and shrinks to the k-th best so far; both change the work, never the result
+ * (DESIGN.md §20).
+ * bh_find_knn_bodies: the probes are the N bodies of the list after the build, in caller order
+ * (nothing is uploaded); row i belongs to caller index i.  A body's own leaf is skipped by
+ * identity, so the rows hold the k nearest *other* bodies; a coincident other body is found with
+ * d2 = 0.  A body that is not in S (outside the root cell, dropped by the jitter, or of mass 0) is
+ * a probe like any other and skips nothing.  rows_cap is the room of the arrays in rows:
+ * rows_cap < N returns BH_E_CAPACITY with *n_rows = N (nullable) and the arrays untouched; N = 0
+ * returns BH_OK with *n_rows = 0.
+ * n_probe = 0 returns BH_OK after the build, launches nothing and leaves bh_knn_kernel_ms as it
+ * was.  With no body in the tree every found is 0 and every row is padding.
+ * BH_E_INVALID (with bh_last_error text), before anything is launched: e NULL, n_probe < 0 or
+ * > 2^28, px or py NULL with n_probe > 0, k outside 1..BH_KNN_MAX_K, r_max NaN or negative,
+ * n_probe * k (or N * k) > 2^31 - 1 ("ask in batches"), a negative rows_cap.
+ * BH_E_STATE between bh_step_begin and bh_step_end. */
+#define BH_KNN_MAX_K 64
+int bh_find_knn(bh_engine *e, int64_t n_probe, const double *px, const double *py, int32_t k,
+                double r_max, int64_t *idx, double *d2, int64_t *found);
+int bh_find_knn_bodies(bh_engine *e, int32_t k, double r_max, int64_t *idx, double *d2,
+                       int64_t *found, int64_t rows_cap, int64_t *n_rows);
+
+/* HIP-event duration (ms) of the last bh_find_knn / bh_find_knn_bodies call's device work, from
+ * the seed kernel to the walk's last store (the leaf sequence and the probes' upload, keying and
+ * sort are outside it); 0 before the first. */
+int bh_knn_kernel_ms(const bh_engine *e, double *ms);
+
+/* What the k-nearest walk launches for n_lane probes and lists of k entries (host-only: no
+ * device, no engine; returned by the function the launch itself branches on, as
+ * bh_direct_field_shape's values are): out4 = {lanes per wave, waves per workgroup, LDS bytes per
+ * workgroup, workgroups}.  The waves per workgroup are the field walk's, halved until the
+ * workgroup's lists (waves x 64 lanes x k entries of 12 bytes) fit 64 KiB.
+ * BH_E_INVALID: out4 NULL, n_lane < 0 or > 2^28, k outside 1..BH_KNN_MAX_K. */
+int bh_knn_shape(int64_t n_lane, int32_t k, int64_t *out4);
 
 /* One group of bh_find_groups' catalogue. */
 typedef struct bh_group {
