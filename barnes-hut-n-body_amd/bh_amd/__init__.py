@@ -54,6 +54,7 @@ EXPORTED_SYMBOLS = (
     "bh_find_neighbors", "bh_neighbors_kernel_ms", "bh_neighbor_reach",
     "bh_find_knn", "bh_find_knn_bodies", "bh_knn_kernel_ms", "bh_knn_shape",
     "bh_find_groups", "bh_groups_kernel_ms",
+    "bh_compute_radial_profile", "bh_radial_profile_kernel_ms", "bh_radial_edges",
     "bh_compute_field_direct", "bh_compute_force_error", "bh_direct_field_kernel_ms",
     "bh_direct_field_shape",
     "bh_compute_field_grid", "bh_field_grid_of_view", "bh_field_grid_kernel_ms",
@@ -138,6 +139,107 @@ class BhGroupsSummary(ctypes.Structure):
         ("largest_label", ctypes.c_int64),
         ("largest_count", ctypes.c_int64),
     ]
+
+
+class BhRadialBin(ctypes.Structure):
+    """struct bh_radial_bin (include/bh_engine.h) -- one annulus of bh_compute_radial_profile."""
+    _fields_ = [
+        ("count", ctypes.c_int64),
+        ("mass", ctypes.c_double),
+        ("mr", ctypes.c_double),
+        ("mvr", ctypes.c_double),
+        ("mvt", ctypes.c_double),
+        ("mvr2", ctypes.c_double),
+        ("mvt2", ctypes.c_double),
+        ("lz", ctypes.c_double),
+    ]
+
+
+class BhRadialSummary(ctypes.Structure):
+    """struct bh_radial_summary (include/bh_engine.h)."""
+    _fields_ = [
+        ("n_bodies", ctypes.c_int64),
+        ("n_selected", ctypes.c_int64),
+        ("n_binned", ctypes.c_int64),
+        ("n_inner", ctypes.c_int64),
+        ("n_outer", ctypes.c_int64),
+        ("n_nan", ctypes.c_int64),
+    ]
+
+
+BH_RADIAL_MAX_BINS = 4096
+# bh_radial_bin as a numpy record (the same 64 bytes)
+RADIAL_BIN_DTYPE = np.dtype([("count", "<i8"), ("mass", "<f8"), ("mr", "<f8"), ("mvr", "<f8"),
+                             ("mvt", "<f8"), ("mvr2", "<f8"), ("mvt2", "<f8"), ("lz", "<f8")])
+
+
+@dataclass(frozen=True)
+class RadialSummary:
+    """Engine.radial_profile(): the fields of bh_radial_summary."""
+    n_bodies: int
+    n_selected: int
+    n_binned: int
+    n_inner: int
+    n_outer: int
+    n_nan: int
+
+
+class RadialProfile:
+    """Engine.radial_profile(): the edges (n_bin + 1), the raw columns of bh_radial_bin as numpy
+    arrays (`bins` is the structured array itself), the summary, and derived read-outs made on
+    the host with numpy, one formula each; the means and dispersions of an empty bin are NaN
+    (0 / 0), not an exception, its surface density 0."""
+
+    def __init__(self, edges, bins, summary: RadialSummary):
+        self.edges = edges
+        self.bins = bins
+        self.summary = summary
+        for name in RADIAL_BIN_DTYPE.names:
+            setattr(self, name, np.ascontiguousarray(bins[name]))
+
+    @staticmethod
+    def _over(a, b):
+        with np.errstate(all="ignore"):  # (an empty bin: 0 / 0 = NaN)
+            return a / b
+
+    @property
+    def surface_density(self):
+        """mass / (pi * (e[k+1]**2 - e[k]**2))"""
+        e = self.edges
+        with np.errstate(all="ignore"):
+            return self.mass / (np.pi * (e[1:] ** 2 - e[:-1] ** 2))
+
+    @property
+    def v_rot(self):
+        """mvt / mass"""
+        return self._over(self.mvt, self.mass)
+
+    @property
+    def v_rad(self):
+        """mvr / mass"""
+        return self._over(self.mvr, self.mass)
+
+    @property
+    def sigma_r(self):
+        """sqrt(mvr2 / mass - v_rad**2)"""
+        with np.errstate(all="ignore"):
+            return np.sqrt(self._over(self.mvr2, self.mass) - self.v_rad ** 2)
+
+    @property
+    def sigma_t(self):
+        """sqrt(mvt2 / mass - v_rot**2)"""
+        with np.errstate(all="ignore"):
+            return np.sqrt(self._over(self.mvt2, self.mass) - self.v_rot ** 2)
+
+    @property
+    def mean_r(self):
+        """mr / mass"""
+        return self._over(self.mr, self.mass)
+
+    @property
+    def enclosed_mass(self):
+        """cumsum(mass): the mass of the selected bodies in bins 0..k"""
+        return np.cumsum(self.mass)
 
 
 # bh_group as a numpy record (the same 64 bytes)
@@ -335,6 +437,12 @@ def load_library(path: str | None = None):
                                    _I64P, ctypes.c_int64, ctypes.POINTER(BhGroup),
                                    ctypes.c_int64, ctypes.POINTER(BhGroupsSummary)]
     lib.bh_groups_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_compute_radial_profile.argtypes = [_VP] + [ctypes.c_double] * 4 + [
+        ctypes.c_int32, _D, _I64P, ctypes.c_int64, ctypes.POINTER(BhRadialBin),
+        ctypes.POINTER(BhRadialSummary)]
+    lib.bh_radial_profile_kernel_ms.argtypes = [_VP, _D]
+    lib.bh_radial_edges.argtypes = [ctypes.c_double, ctypes.c_double, ctypes.c_int32,
+                                    ctypes.c_int, _D]
     lib.bh_compute_field_direct.argtypes = [_VP, ctypes.c_int64, _D, _D, _D, _D, _D, _D]
     lib.bh_compute_force_error.argtypes = [_VP, ctypes.c_int64, _I64P, _D, _D, _D, _D,
                                            ctypes.POINTER(BhForceError)]
@@ -528,6 +636,18 @@ def neighbor_reach(depth: int, params: BhParams | None = None) -> float:
     if rc != BH_OK:
         raise BhError(rc, "bh_neighbor_reach: invalid arguments")
     return out.value
+
+
+def radial_edges(r_min: float, r_max: float, n_bin: int, log: bool = False) -> np.ndarray:
+    """n_bin + 1 bin edges from r_min to r_max, linear or (log=True, r_min > 0) logarithmic, end
+    points exact (bh_radial_edges; host-only, no device)."""
+    n_bin = int(n_bin)
+    out = np.zeros(max(n_bin, 0) + 1, dtype=np.float64)
+    lib = load_library()
+    rc = lib.bh_radial_edges(float(r_min), float(r_max), n_bin, 1 if log else 0, _dp(out))
+    if rc != BH_OK:
+        raise BhError(rc, lib.bh_last_error(None).decode())
+    return out
 
 
 def field_grid_shape(nx: int, ny: int):
@@ -1036,6 +1156,32 @@ class Engine:
         """HIP-event time (ms) of the last find_groups call's device work, link walk to last
         catalogue kernel (bh_groups_kernel_ms)."""
         return self._kernel_ms(self._lib.bh_groups_kernel_ms)
+
+    def radial_profile(self, cx, cy, edges, cvx=0.0, cvy=0.0, subset=None) -> RadialProfile:
+        """bh_compute_radial_profile: the bodies in the annuli edges[k] <= R < edges[k+1] about
+        (cx, cy), velocities taken relative to (cvx, cvy): per bin the count and the fixed-order
+        sums of m, m R, m vr, m vt, m vr^2, m vt^2 and m w.  subset: list indices (a set: a
+        duplicate counts once; empty selects nothing), None for every body.  No build, no
+        jitter, no state change: it reads what get_bodies() returns now."""
+        e = np.ascontiguousarray(edges, dtype=np.float64).reshape(-1)
+        n_bin = len(e) - 1
+        sub = None if subset is None else np.ascontiguousarray(subset, dtype=np.int64).reshape(-1)
+        # (an empty array may have a null data pointer: the subset is told by the pointer)
+        sub_arg = None if sub is None else np.concatenate([sub, np.zeros(1, dtype=np.int64)])
+        bins = np.zeros(max(n_bin, 1), dtype=RADIAL_BIN_DTYPE)
+        sm = BhRadialSummary()
+        self._check(self._lib.bh_compute_radial_profile(
+            self._h, float(cx), float(cy), float(cvx), float(cvy), n_bin, _dp(e),
+            None if sub is None else sub_arg.ctypes.data_as(_I64P), 0 if sub is None else len(sub),
+            bins.ctypes.data_as(ctypes.POINTER(BhRadialBin)), ctypes.byref(sm)))
+        summary = RadialSummary(int(sm.n_bodies), int(sm.n_selected), int(sm.n_binned),
+                                int(sm.n_inner), int(sm.n_outer), int(sm.n_nan))
+        return RadialProfile(e, bins[:max(n_bin, 0)], summary)
+
+    def radial_profile_kernel_ms(self) -> float:
+        """HIP-event time (ms) of the last radial_profile call's device work, staging to last
+        emit kernel (bh_radial_profile_kernel_ms)."""
+        return self._kernel_ms(self._lib.bh_radial_profile_kernel_ms)
 
     def compute_field_direct(self, px, py, pm=None, want_accel=True, want_phi=True):
         """bh_compute_field_direct: compute_field with no cell ever accepted, whatever the
@@ -1580,6 +1726,23 @@ class PhysicsEngine:
         bs = self._bodies
         return [[bs[int(c)] for c in mem[int(g["first"]):int(g["first"] + g["count"])]]
                 for g in cat]
+
+    def profile(self, x, y, edges, vx=0.0, vy=0.0, bodies=None) -> RadialProfile:
+        """The radial profile of the caller's list about (x, y) in the frame moving with
+        (vx, vy) (Engine.radial_profile).  bodies: the caller's own Body objects to select, told
+        by identity -- one list of groups(), for instance -- else every body.  Nothing is pulled
+        back: the call changes nothing."""
+        self._eng.set_params(self._params())
+        if self._changed():
+            self._push()
+        subset = None
+        if bodies is not None:
+            at = {id(b): i for i, b in enumerate(self._bodies)}
+            try:
+                subset = [at[id(b)] for b in bodies]
+            except KeyError:
+                raise ValueError("profile: a body of `bodies` is not in the engine's list") from None
+        return self._eng.radial_profile(float(x), float(y), edges, float(vx), float(vy), subset)
 
     getBodies = get_bodies
     resetBodies = reset_bodies

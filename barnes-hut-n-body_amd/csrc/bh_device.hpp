@@ -880,6 +880,33 @@ hipError_t groups_run(const Node *nodes, size_t node_cap, const uint32_t *d_T,
                       int64_t min_members, const NeighborReach &rc, const GroupBufs &B,
                       hipStream_t s);
 
+// ---- launchers (radial_profile.hip): the bodies in annuli about a centre -------------------
+// The working set of bh_compute_radial_profile for a list of n bodies (the engine allocates it;
+// every plane that depends on the bin count is sized for BH_RADIAL_MAX_BINS).
+struct RadialBufs {
+    double *edges;           // n_bin + 1, uploaded by the caller of radial_run
+    uint8_t *flag;           // n: 1 for a caller index of the subset (used with a subset only)
+    uint32_t *key, *key_s;   // n: the bin, or one of the four class keys above it; as sorted
+    uint32_t *val, *val_s;   // n: the caller index
+    uint32_t *start;         // n_bin + 5: where key k begins in the sorted keys; the last is n
+    double *terms;           // 7 planes of n, by sorted position
+    double *part;            // 7 planes of radial_partial_slots(n): the blocks' partial sums
+    bh_radial_bin *bins;     // n_bin
+    void *scratch;           // radial_scratch_bytes(n): the sort
+    size_t scratch_bytes;
+};
+size_t radial_partial_slots(int64_t n);
+size_t radial_scratch_bytes(int64_t n);
+// The classes above the bins in `start`: start[n_bin + RADIAL_INNER] .. and so on.
+enum { RADIAL_INNER = 0, RADIAL_OUTER = 1, RADIAL_NAN = 2, RADIAL_UNSELECTED = 3 };
+// x .. m: the n bodies in the caller's list order.  selected: the selection is the set of the
+// n_subset caller indices at subset (device; each in [0, n)), else every body.  Keys, one stable sort, bin starts and -- with
+// want_bins -- terms, block partials and B.bins, all on the stream; B.start is complete either way.
+hipError_t radial_run(int64_t n, const double *x, const double *y, const double *vx,
+                      const double *vy, const double *m, double cx, double cy, double cvx,
+                      double cvy, int32_t n_bin, bool selected, const int64_t *subset,
+                      int64_t n_subset, bool want_bins, const RadialBufs &B, hipStream_t s);
+
 // ---- launchers (render.hip) ------------------------------------------------------
 // The body pass of a frame (PNL:302-307).  Working planes `packed` and `cnt` (null: no density):
 // render_padded_pixels() uint32 each, zero on entry to render_raster and zero again after

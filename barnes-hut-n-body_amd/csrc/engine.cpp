@@ -566,6 +566,19 @@ struct bh_engine {
     std::atomic<int> prog_site{0}, prog_busy{0};
 
     std::string err;
+
+    // bh_compute_radial_profile (radial_profile.hip): the call's own buffers, allocated on first
+    // use and grown when the list outgrows them (rad_cap bodies; the planes that depend on the bin
+    // count are sized for BH_RADIAL_MAX_BINS) or the subset does (rad_sub_cap entries)
+    uint32_t *rad_u32 = nullptr;   // key, sorted key, index, sorted index; the keys' starts
+    uint8_t *rad_flag = nullptr;   // the subset's marks, by caller index
+    double *rad_f64 = nullptr;     // the seven term planes; the blocks' partial sums; the edges
+    bh_radial_bin *rad_bins = nullptr;
+    int64_t *rad_sub = nullptr;    // the uploaded subset
+    void *rad_scratch = nullptr;   // the sort
+    size_t rad_scratch_bytes = 0;
+    int64_t rad_cap = 0, rad_sub_cap = 0;
+    Stopwatch rad_sw;  // from the staging in list order to the last emit kernel
 };
 
 namespace {
@@ -3821,12 +3834,13 @@ void bh_destroy(bh_engine *e) {
                     e->nbr_list, e->nbr_sort, e->knn_in, e->knn_u32, e->knn_scratch, e->knn_seed,
                     e->knn_found, e->knn_idx, e->knn_d2,
                     e->grp_u32, e->grp_u64, e->grp_i64, e->grp_part, e->grp_groups, e->grp_scratch,
+                    e->rad_u32, e->rad_flag, e->rad_f64, e->rad_bins, e->rad_sub, e->rad_scratch,
                     e->trc, e->trc_snap, e->trc_u32, e->trc_scratch, e->slog_ring, e->slog_phi,
                     e->slog_stage, e->slog_part, e->slog_keep, e->slog_pos, e->slog_tmp};
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (Stopwatch *sw : {&e->pot_sw, &e->fld_sw, &e->dfl_sw, &e->fgr_sw, &e->nbr_sw, &e->knn_sw, &e->grp_sw,
-                          &e->grp_sw_run, &e->rnd_sw, &e->qd_sw})
+                          &e->grp_sw_run, &e->rad_sw, &e->rnd_sw, &e->qd_sw})
         sw->destroy();
     for (hipEvent_t ev : e->ev) (void)hipEventDestroy(ev);
     if (e->lr_ev) (void)hipEventDestroy(e->lr_ev);
@@ -4692,6 +4706,165 @@ int bh_find_groups(bh_engine *e, double link, int64_t min_members, int64_t *labe
 
 int bh_groups_kernel_ms(const bh_engine *e, double *ms) {
     return kernel_ms(e, &bh_engine::grp_sw, ms);
+}
+
+// What bh_compute_radial_profile refuses its edges for (null: nothing).
+static const char *radial_edges_error(int32_t n_bin, const double *edges) {
+    if (!edges) return "edges is NULL";
+    if (n_bin < 1 || n_bin > BH_RADIAL_MAX_BINS) return "n_bin must be in 1..BH_RADIAL_MAX_BINS";
+    for (int32_t k = 0; k <= n_bin; ++k)
+        if (std::isnan(edges[k])) return "an edge is NaN";
+    if (edges[0] < 0.0) return "edges[0] must be >= 0";
+    for (int32_t k = 0; k < n_bin; ++k)
+        if (!(edges[k] < edges[k + 1])) return "edges must be strictly increasing";
+    return nullptr;
+}
+
+// The planes of bh_compute_radial_profile's buffers for the engine's rad_cap.
+static RadialBufs radial_bufs(const bh_engine *e) {
+    const size_t cap = (size_t)e->rad_cap;
+    RadialBufs B{};
+    B.key = e->rad_u32;
+    B.key_s = B.key + cap;
+    B.val = B.key_s + cap;
+    B.val_s = B.val + cap;
+    B.start = B.val_s + cap;
+    B.flag = e->rad_flag;
+    B.terms = e->rad_f64;
+    B.part = B.terms + 7 * cap;
+    B.edges = B.part + 7 * radial_partial_slots(e->rad_cap);
+    B.bins = e->rad_bins;
+    B.scratch = e->rad_scratch;
+    B.scratch_bytes = e->rad_scratch_bytes;
+    return B;
+}
+
+// The caller-visible state (as diagnostics_state reads and stages it) binned: nothing of the
+// state or of what the pipelined engine carries into the next call is written.  The arguments
+// have been validated.
+static int radial_state(bh_engine *e, double cx, double cy, double cvx, double cvy, int32_t n_bin,
+                        const double *edges, const int64_t *subset, int64_t n_subset,
+                        bh_radial_bin *bins, bh_radial_summary *summary) {
+    const int64_t n = e->n;
+    if (n <= 0 || (!bins && !summary)) {  // nothing to bin, or nothing asked for: no device work
+        if (bins) std::memset(bins, 0, sizeof(bh_radial_bin) * (size_t)n_bin);
+        if (summary) *summary = bh_radial_summary{};
+        return BH_OK;
+    }
+    HIPCHK(e, hipSetDevice(e->device));
+    if (outgrown(e->rad_cap, e->rad_u32, n)) {
+        const size_t cap = (size_t)n;
+        TRY(dev_alloc(e, e->rad_u32, 4 * cap + BH_RADIAL_MAX_BINS + 5));
+        TRY(dev_alloc(e, e->rad_flag, cap));
+        TRY(dev_alloc(e, e->rad_f64,
+                      7 * cap + 7 * radial_partial_slots(n) + BH_RADIAL_MAX_BINS + 1));
+        TRY(dev_alloc(e, e->rad_bins, (size_t)BH_RADIAL_MAX_BINS));
+        if (e->rad_scratch) (void)hipFree(e->rad_scratch);
+        e->rad_scratch = nullptr;
+        e->rad_scratch_bytes = radial_scratch_bytes(n);
+        HIPCHK(e, hipMalloc(&e->rad_scratch, e->rad_scratch_bytes ? e->rad_scratch_bytes : 1));
+        e->rad_cap = n;
+    }
+    if (subset && n_subset > 0 && outgrown(e->rad_sub_cap, e->rad_sub, n_subset)) {
+        TRY(dev_alloc(e, e->rad_sub, (size_t)n_subset));
+        e->rad_sub_cap = n_subset;
+    }
+    // (the planes are laid out for rad_cap; the kernels run over the first n entries of each)
+    const RadialBufs B = radial_bufs(e);
+    TRY(materialize_positions(e));
+    HIPCHK(e, hipMemcpyAsync(B.edges, edges, sizeof(double) * ((size_t)n_bin + 1),
+                             hipMemcpyHostToDevice, e->stream));
+    if (subset && n_subset > 0)
+        HIPCHK(e, hipMemcpyAsync(e->rad_sub, subset, sizeof(int64_t) * (size_t)n_subset,
+                                 hipMemcpyHostToDevice, e->stream));
+    const BodyState &s = e->view_pending ? e->view : e->st;  // (not the prebuilt tree's jitter)
+    const double *src[5] = {s.x, s.y, s.vx, s.vy, s.m};
+    double *stage[5] = {e->alt.x, e->alt.y, e->alt.vx, e->alt.vy, e->alt.m};
+    TRY(e->rad_sw.start(e, e->stream));
+    scatter_to_caller(n, s.cidx, 5, src, stage, e->stream);
+    HIPCHK(e, hipGetLastError());
+    HIPCHK(e, radial_run(n, e->alt.x, e->alt.y, e->alt.vx, e->alt.vy, e->alt.m, cx, cy, cvx, cvy,
+                         n_bin, subset != nullptr, e->rad_sub, subset ? n_subset : 0,
+                         bins != nullptr, B, e->stream));
+    TRY(e->rad_sw.stop(e, e->stream));
+    uint32_t cls[5];  // where the four classes begin in the sorted keys, and n
+    HIPCHK(e, hipMemcpyAsync(cls, B.start + n_bin, sizeof(cls), hipMemcpyDeviceToHost, e->stream));
+    if (bins)
+        HIPCHK(e, hipMemcpyAsync(bins, B.bins, sizeof(bh_radial_bin) * (size_t)n_bin,
+                                 hipMemcpyDeviceToHost, e->stream));
+    SYNC(e, e->stream);
+    if (summary) {
+        summary->n_bodies = n;
+        summary->n_selected = (int64_t)cls[RADIAL_UNSELECTED];
+        summary->n_binned = (int64_t)cls[RADIAL_INNER];
+        summary->n_inner = (int64_t)(cls[RADIAL_OUTER] - cls[RADIAL_INNER]);
+        summary->n_outer = (int64_t)(cls[RADIAL_NAN] - cls[RADIAL_OUTER]);
+        summary->n_nan = (int64_t)(cls[RADIAL_UNSELECTED] - cls[RADIAL_NAN]);
+    }
+    return BH_OK;
+}
+
+int bh_compute_radial_profile(bh_engine *e, double cx, double cy, double cvx, double cvy,
+                              int32_t n_bin, const double *edges, const int64_t *subset,
+                              int64_t n_subset, bh_radial_bin *bins, bh_radial_summary *summary) {
+    if (!e) return BH_E_INVALID;
+    ASYNC_GUARD(e);
+    const char *bad = radial_edges_error(n_bin, edges);
+    if (!bad && subset) {
+        const int64_t N = bh_num_bodies(e);
+        if (n_subset < 0 || n_subset > ((int64_t)1 << 28)) bad = "n_subset must be in [0, 2^28]";
+        for (int64_t j = 0; !bad && j < n_subset; ++j)
+            if (subset[j] < 0 || subset[j] >= N) bad = "a subset index is outside [0, N)";
+    }
+    if (bad) {
+        e->err = std::string("bh_compute_radial_profile: ") + bad;
+        return BH_E_INVALID;
+    }
+    if (e->multi) {  // every replica is complete at the API boundary: member 0's
+        const int rc = bh_compute_radial_profile(MULTI_M0(e), cx, cy, cvx, cvy, n_bin, edges,
+                                                 subset, n_subset, bins, summary);
+        if (rc != BH_OK) e->err = bh_last_error(MULTI_M0(e));
+        return rc;
+    }
+    COMM_GUARD(e);
+    return radial_state(e, cx, cy, cvx, cvy, n_bin, edges, subset, n_subset, bins, summary);
+}
+
+int bh_radial_profile_kernel_ms(const bh_engine *e, double *ms) {
+    return kernel_ms(e, &bh_engine::rad_sw, ms);
+}
+
+int bh_radial_edges(double r_min, double r_max, int32_t n_bin, int log_spacing, double *edges) {
+    handleless_error = nullptr;
+    const char *bad = nullptr;
+    if (!edges) bad = "bh_radial_edges: edges is NULL";
+    else if (n_bin < 1 || n_bin > BH_RADIAL_MAX_BINS)
+        bad = "bh_radial_edges: n_bin must be in 1..BH_RADIAL_MAX_BINS";
+    else if (!std::isfinite(r_min) || r_min < 0.0)
+        bad = "bh_radial_edges: r_min must be finite and >= 0";
+    else if (log_spacing && !(r_min > 0.0))
+        bad = "bh_radial_edges: log spacing needs r_min > 0";
+    else if (!std::isfinite(r_max) || !(r_max > r_min))
+        bad = "bh_radial_edges: r_max must be finite and above r_min";
+    if (bad) {
+        handleless_error = bad;
+        return BH_E_INVALID;
+    }
+    std::vector<double> out((size_t)n_bin + 1);
+    const double span = log_spacing ? std::log2(r_max / r_min) : r_max - r_min;
+    for (int32_t k = 1; k < n_bin; ++k)
+        out[(size_t)k] = log_spacing ? r_min * std::exp2(span * (double)k / (double)n_bin)
+                                     : r_min + span * ((double)k / (double)n_bin);
+    out[0] = r_min;
+    out[(size_t)n_bin] = r_max;
+    for (int32_t k = 0; k < n_bin; ++k)
+        if (!(out[(size_t)k] < out[(size_t)k + 1])) {
+            handleless_error = "bh_radial_edges: the edges are not strictly increasing (bins "
+                               "narrower than the spacing of binary64)";
+            return BH_E_INVALID;
+        }
+    std::memcpy(edges, out.data(), sizeof(double) * out.size());
+    return BH_OK;
 }
 
 int bh_neighbor_reach(const bh_params *p, int32_t depth, double *reach) {

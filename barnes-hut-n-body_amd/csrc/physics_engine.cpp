@@ -335,6 +335,33 @@ std::vector<std::vector<Body *>> PhysicsEngine::groups(double link, int64_t minM
     return out;
 }
 
+bh_radial_summary PhysicsEngine::profile(double x, double y, const std::vector<double> &edges,
+                                         std::vector<bh_radial_bin> &bins, double vx, double vy,
+                                         const std::vector<Body *> *bodies) {
+    if (edges.size() < 2) throw std::runtime_error("profile: edges needs at least two entries");
+    pushParams();
+    if ((int64_t)bodies_->size() != mirN_ || bodiesChanged()) pushBodies();  // the caller's edits
+    std::vector<int64_t> subset;
+    if (bodies) {
+        subset.reserve(bodies->size() + 1);
+        for (const Body *b : *bodies) {
+            if (b < bodies_->data() || b >= bodies_->data() + bodies_->size())
+                throw std::runtime_error("profile: a body of `bodies` is not in the engine's list");
+            subset.push_back((int64_t)(b - bodies_->data()));
+        }
+        subset.push_back(0);  // (never read: an empty selection still has a pointer)
+    }
+    const int32_t nBin = edges.size() - 1 > (size_t)BH_RADIAL_MAX_BINS + 1
+                             ? BH_RADIAL_MAX_BINS + 1  // (refused by the call)
+                             : (int32_t)(edges.size() - 1);
+    bins.assign((size_t)nBin, bh_radial_bin{});
+    bh_radial_summary sum{};
+    check(bh_compute_radial_profile(eng_, x, y, vx, vy, nBin, edges.data(),
+                                    bodies ? subset.data() : nullptr,
+                                    bodies ? (int64_t)bodies->size() : 0, bins.data(), &sum));
+    return sum;
+}
+
 void PhysicsEngine::setTracers(const std::vector<double> &x, const std::vector<double> &y,
                                const std::vector<double> &vx, const std::vector<double> &vy) {
     const size_t n = x.size();

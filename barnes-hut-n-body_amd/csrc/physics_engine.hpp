@@ -129,6 +129,16 @@ public:
     // pointers are into that list.
     std::vector<std::vector<Body *>> groups(double link, int64_t minMembers = 2);
 
+    // The radial profile of the caller's list about (x, y) in the frame moving with (vx, vy)
+    // (bh_compute_radial_profile; no reference counterpart): bins is resized to edges.size() - 1
+    // records, bin k holding the bodies with edges[k] <= R < edges[k + 1]; the summary is
+    // returned.  bodies (nullable): pointers into the caller's list that select the population --
+    // one list of groups(), for instance -- else every body.  Only reads the state: nothing is
+    // written back into the list.
+    bh_radial_summary profile(double x, double y, const std::vector<double> &edges,
+                              std::vector<bh_radial_bin> &bins, double vx = 0.0, double vy = 0.0,
+                              const std::vector<Body *> *bodies = nullptr);
+
     // Tracers (bh_set_tracers; no reference counterpart): massless test particles of mass 1.0 that
     // every step() carries along on the bodies' own trees and that exert nothing.  A list of the
     // engine's own, kept across resetBodies; vx, vy empty: zeros; empty x, y: no tracers.

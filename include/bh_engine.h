@@ -200,7 +200,7 @@ int bh_step(bh_engine *e, int32_t k);
  * buffer) and call bh_step_positions (bh_step, bh_reset_bodies, bh_set_params, bh_get_bodies,
  * bh_map_bodies, bh_set_mirror, bh_get_quads, bh_compute_accelerations, bh_compute_potential,
  * bh_compute_field, bh_compute_field_direct, bh_compute_force_error, bh_compute_field_grid,
- * bh_find_neighbors, bh_find_knn, bh_find_knn_bodies, bh_find_groups,
+ * bh_find_neighbors, bh_find_knn, bh_find_knn_bodies, bh_find_groups, bh_compute_radial_profile,
  * bh_compute_diagnostics and bh_render_bodies return BH_E_STATE); bh_step_end joins and returns bh_step's result (then
  * bh_last_removed, bh_map_bodies, ... as after bh_step).  bh_render_quads is refused in the same
  * way, as bh_get_quads is, and so are bh_set_tracers, bh_get_tracers and bh_render_tracers, and
@@ -528,6 +528,88 @@ int bh_find_groups(bh_engine *e, double link, int64_t min_members,
  * walk's start to the last catalogue kernel (the build, the leaf sequence and the copy-out are
  * outside it); 0 before the first call that found a non-empty S. */
 int bh_groups_kernel_ms(const bh_engine *e, double *ms);
+
+/* One annulus of bh_compute_radial_profile. */
+typedef struct bh_radial_bin {      /* 64 bytes */
+    int64_t count;                  /* selected bodies with edges[k] <= R < edges[k+1] */
+    double mass;                    /* sum m                    */
+    double mr;                      /* sum m*R                  */
+    double mvr, mvt;                /* sum m*vr, sum m*vt       */
+    double mvr2, mvt2;              /* sum (m*vr)*vr, sum (m*vt)*vt */
+    double lz;                      /* sum m*w                  */
+} bh_radial_bin;
+
+typedef struct bh_radial_summary {  /* 48 bytes */
+    int64_t n_bodies;    /* N of the list */
+    int64_t n_selected;  /* N, or the number of distinct indices in subset */
+    int64_t n_binned;    /* selected bodies that fell into a bin */
+    int64_t n_inner;     /* selected, R < edges[0] */
+    int64_t n_outer;     /* selected, R >= edges[n_bin] (R = +inf included) */
+    int64_t n_nan;       /* selected, R is NaN */
+} bh_radial_summary;
+
+#define BH_RADIAL_MAX_BINS 4096
+/* The bodies of the current state in annuli about a centre: per bin the count and the sums from
+ * which the surface density, the rotation curve, the velocity dispersions and the enclosed mass
+ * of a disk follow, without copying the bodies out.  The centre (cx, cy) and the frame velocity
+ * (cvx, cvy) are the caller's -- a group's mx / mass, my / mass, px / mass, py / mass from
+ * bh_find_groups, for instance, with that group's members as the subset.
+ * State and errors as bh_compute_diagnostics(e, 0, ...): no build, no jitter, no state change; the
+ * call reads the state the caller sees (what bh_get_bodies returns now), never the jittered
+ * positions of a tree the engine built ahead, and covers every live body of the list: bodies
+ * outside the root cell and bodies of mass 0 or of negative mass are in.  A multi-device handle
+ * answers from member 0's replica.
+ * Selection.  subset == NULL: every body (n_subset is ignored).  Else the set of the caller
+ * indices subset[0 .. n_subset): a duplicate counts once, n_subset = 0 selects nothing.  Indices
+ * refer to the list bh_get_bodies returns now.
+ * The terms of body c, in binary64, every operation separate, never fused:
+ *     dx = x - cx;  dy = y - cy;  R2 = dx*dx + dy*dy;  R = sqrt(R2)        (IEEE sqrt)
+ *     ux = vx - cvx;  uy = vy - cvy
+ *     u = dx*ux + dy*uy;  w = dx*uy - dy*ux
+ *     vr = u / R;  vt = w / R        (IEEE divide);  if R2 == 0.0: vr = vt = +0.0
+ *     terms: m, m*R, m*vr, m*vt, (m*vr)*vr, (m*vt)*vt, m*w
+ * R2 == 0 is the one special case (the natural centre is the central body's own position, and 0/0
+ * would poison bin 0); nothing else is: a non-finite centre or frame velocity, a coordinate of
+ * 1e300 and a NaN coordinate give what this arithmetic gives.
+ * Bins.  edges[0 .. n_bin] are strictly increasing, edges[0] >= 0; edges[n_bin] may be +inf.
+ * Body c is in bin k iff edges[k] <= R && R < edges[k+1]: the lower edge is inclusive and the
+ * compare is on R itself.  R < edges[0] counts in n_inner, R >= edges[n_bin] (an R of +inf even
+ * under a last edge of +inf) in n_outer, a NaN R is in no bin and counts in n_nan.
+ * Sums.  Bin k's selected members in ascending caller index are c0 < c1 < ...; block j holds
+ * members [256j, 256j + 256) of that list, its partial is the sequential sum of its terms in that
+ * order from +0.0, and the bin's value is the sequential sum of its block partials in order from
+ * +0.0 -- bh_group's rule with the bin as the label.  No floating-point atomic is used anywhere:
+ * two calls, two engines holding the same list, or a multi-device handle return identical bytes.
+ * An empty bin is all zeros (+0.0).
+ * Outputs: bins (n_bin records) and summary are each nullable; with both NULL the call validates
+ * its arguments and launches nothing.  N = 0: BH_OK, all zeros, nothing launched and
+ * bh_radial_profile_kernel_ms left as it was.
+ * Left out on purpose: tracers as the population, per-bin azimuthal harmonics and
+ * a profile per group in one call.
+ * BH_E_INVALID (with bh_last_error text), before anything is launched: e NULL, edges NULL, n_bin
+ * outside 1..BH_RADIAL_MAX_BINS, an edge that is NaN, edges[0] < 0, edges not strictly increasing,
+ * subset non-NULL with n_subset < 0 or > 2^28, a subset index outside [0, N).  BH_E_STATE between
+ * bh_step_begin and bh_step_end. */
+int bh_compute_radial_profile(bh_engine *e, double cx, double cy, double cvx, double cvy,
+                              int32_t n_bin, const double *edges,        /* n_bin + 1 */
+                              const int64_t *subset, int64_t n_subset,   /* NULL: every body */
+                              bh_radial_bin *bins,                       /* n_bin, nullable */
+                              bh_radial_summary *summary);               /* nullable */
+
+/* HIP-event duration (ms) of the last bh_compute_radial_profile call's own device work, from the
+ * staging of the state in list order to the last emit kernel (the uploads of edges and subset
+ * and the copy-out are outside it); 0 before the first call that launched anything. */
+int bh_radial_profile_kernel_ms(const bh_engine *e, double *ms);
+
+/* n_bin + 1 bin edges from r_min to r_max (host-only, no handle).  Linear:
+ *     edges[k] = r_min + (r_max - r_min) * ((double)k / (double)n_bin),  0 < k < n_bin
+ * log_spacing != 0 (needs r_min > 0):
+ *     edges[k] = r_min * exp2(log2(r_max / r_min) * k / n_bin)          (the host's libm)
+ * with edges[0] = r_min and edges[n_bin] = r_max exact in both.
+ * BH_E_INVALID: edges NULL, n_bin outside 1..BH_RADIAL_MAX_BINS, r_min not finite or negative
+ * (or not positive with log_spacing), r_max <= r_min, NaN or +inf, a result that is not strictly
+ * increasing (bins narrower than the spacing of binary64 there). */
+int bh_radial_edges(double r_min, double r_max, int32_t n_bin, int log_spacing, double *edges);
 
 /* The exact field of the current state at n_probe points: bh_compute_field with no cell ever
  * accepted, whatever the engine's theta.  Arguments, probe semantics (a probe is not in the tree;
