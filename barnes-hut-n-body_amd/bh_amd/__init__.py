@@ -575,7 +575,7 @@ def gather_slot(n: int, world: int, lane: int) -> int:
 LAUNCH_PLAN_FIELDS = (
     "small_front", "small_front_p", "cell_depth", "sort_buckets", "com_chunks", "span_groups",
     "own_scan", "bfs", "bfs_bits", "bpw", "wpb", "xcd_groups", "kick_bpw", "kick_wpb",
-    "kick_xcd_groups", "order_runs",
+    "kick_xcd_groups", "order_runs", "node_addr64",
 )
 
 

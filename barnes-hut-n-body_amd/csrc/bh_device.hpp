@@ -455,8 +455,10 @@ struct WalkShape {
 };
 WalkShape walk_shape(int64_t lanes, bool full_waves = false);
 // Whether the walks address node records by a 32-bit byte offset (cursor_walk.hpp nload_off): while
-// the array stays below the limit, 4 GiB.  (A diagnostic build with the limit 0 sends every walk
-// down the 64-bit address form, which no real tree of a test reaches.)
+// the array stays below the limit, 4 GiB, which a real tree passes at 11 184 806 bodies with the
+// default parameters (bh_launch_plan reads the form out as BH_PLAN_NODE_ADDR64).  The Makefile's
+// second library, lib_addr64/, is built with the limit 0, so that every walk of a small tree
+// takes the 64-bit address form; tests/test_gpu_addr64.py runs the suite's walks against it.
 #ifndef BH_NODE_OFF32_LIMIT
 #define BH_NODE_OFF32_LIMIT (size_t(1) << 32)
 #endif

@@ -5675,6 +5675,7 @@ int bh_launch_plan(const bh_params *p, int64_t n, int64_t *out, int64_t cap, int
         f[BH_PLAN_KICK_WPB] = t2.wpb;
         f[BH_PLAN_KICK_XCD_GROUPS] = t2.xcd_full;
         f[BH_PLAN_ORDER_RUNS] = (int64_t)wave_order_runs(n);
+        f[BH_PLAN_NODE_ADDR64] = node_off32(ncap) ? 0 : 1;
     }
     for (int64_t i = 0; i < cap && i < BH_PLAN_FIELDS; ++i) out[i] = f[i];
     return BH_OK;

@@ -1010,7 +1010,10 @@ int64_t bh_gather_slot(int64_t n, int world, int64_t lane);
  * traversal itself branches on, so the read-out moves with the code; tests take their sizes from
  * where it changes.  out receives min(cap, BH_PLAN_FIELDS) values, *n_out = BH_PLAN_FIELDS;
  * n = 0: all zero.  The build's fields describe every build after an engine's first (which has
- * no splitters yet and sorts with the library's radix sort). */
+ * no splitters yet and sorts with the library's radix sort).  BH_PLAN_NODE_ADDR64 describes every
+ * tree walk of that engine, the queries' included: 0 while its node array (32 bytes a record)
+ * stays below 4 GiB and a 32-bit byte offset reaches every record.  An engine's capacity never
+ * shrinks, so one that once held a longer list keeps the form of that list. */
 enum {
     BH_PLAN_SMALL_FRONT = 0, /* 1: the build's front (keys, sort, prefix lengths) is one workgroup */
     BH_PLAN_SMALL_FRONT_P,   /* its sort width, the next power of two >= n (0: front is off)      */
@@ -1028,6 +1031,7 @@ enum {
     BH_PLAN_KICK_WPB,        /* kick-only walk: waves per workgroup                                */
     BH_PLAN_KICK_XCD_GROUPS, /* kick-only walk: whole remapped groups (the tail is not remapped)  */
     BH_PLAN_ORDER_RUNS,      /* runs of waves that a wave order would permute (0: too many)       */
+    BH_PLAN_NODE_ADDR64,     /* 1: the walks fetch node records by a 64-bit address (array >= 4 GiB) */
     BH_PLAN_FIELDS
 };
 int bh_launch_plan(const bh_params *p, int64_t n, int64_t *out, int64_t cap, int64_t *n_out);

@@ -90,12 +90,14 @@ def test_plan_is_host_only_and_sized():
 
 def test_every_field_changes_below_70000():
     for f in FIELDS:
-        if f in ("span_groups", "own_scan"):  # their switches lie higher
+        if f in ("span_groups", "own_scan", "node_addr64"):  # their switches lie higher
             continue
         assert field_boundaries(f, 1, 70_000), f"{f} never changes for n in [1, 70 000]"
 
 
 def test_high_switches_exist():
+    # (node_addr64 switches once, past 10^7 bodies: tests/test_node_addressing.py)
+    assert not field_boundaries("node_addr64", 1, 5_000_000)
     assert len(field_boundaries("span_groups", 70_000, 5_000_000)) >= 1
     assert len(field_boundaries("own_scan", 70_000, 5_000_000)) == 1
     assert len(field_boundaries("wpb", 70_000, 5_000_000)) == 1
