@@ -40,6 +40,106 @@ namespace {
 // Unlike the force's, the own leaf's term m / sqrt(soft2) is no +-0: it is left out by identity
 // (the exact walk never takes the own leaf; the fast walk does, for its +-0 force).  s is never
 // -0.0 (potential.hip), so a massless node's +-0 term on the fast path leaves it unchanged.
+//
+// The mixed carry (walk<true> without POT).  At a mixed stop -- some active lanes accept the
+// node, others open it -- no block runs: the accepting lanes keep their operands (dx, dy, d2,
+// Gm * mass), park (resume = next) and join the wave-uniform mask pend_m.  The next stop where
+// lanes accept and none opens runs ONE block for its own lanes and the waiting ones, each lane on
+// its own operands, and clears pend_m.  The two sets are disjoint by construction: a waiting lane
+// is parked until the cursor leaves the mixed node's subtree, and every block before that is run
+// by lanes inside it.
+//   Order: a lane has at most one term waiting and adds it before its next one, which can only
+//   come once the cursor has passed the node's `next` -- the same terms in the same order.
+//   Flush: from a mixed node the cursor descends with the lanes that opened it; each stop below
+//   either takes (a block), is mixed again (more lanes wait) or opens for all, and the descent ends
+//   at a leaf or a leaf-flagged massless cell, where every active lane accepts.  (The counting
+//   walk's skipped massless children are no stops, and a cell with mass has a child with mass.)
+//   So no term waits when its lane wakes or the walk ends; the drain after the loop is free.
+// walk<false> keeps the plain block: its identity skip of the own leaf and its massless skip can
+// leave a subtree without a block.  Measured: profiles/r12_mixed_carry_ab.md.
+//
+// The stop's part after the cursor decision, written out.  As C++ -- uniform branches on the three
+// masks around lane-conditional assignments to values that outlive the stop -- it comes back from
+// the compiler with v_cndmask selects and register copies at every stop.  Here a stop no lane
+// accepts at costs what it did (the EXEC save and one branch), the plain block its 29 VALU and two
+// scalar compares that fall through; a mixed stop 6 VALU and no block; a block that takes
+// waiting terms along 4 more.  The block is walk<true>'s own, instruction for instruction as the
+// compiler emits fast_block (fastmath.hpp sqrt_rn_inrange_h, rcp_rn_seeded; the s_nop is the
+// wait state between v_rsq_f64 and its first use): the same operations in the same order.
+//   cm / om: the lanes that accept / open the node;  pend: the waiting lanes (in, out)
+//   (dx, dy, d2): the stop's operands, used up;  (pdx, pdy, pd2, pgm): the waiting lanes' own
+__device__ __forceinline__ void carry_stop(uint64_t cm, uint64_t om, uint64_t &pend, double Gm,
+                                           double mass, uint32_t next, double dx, double dy,
+                                           double d2, double &pdx, double &pdy, double &pd2,
+                                           double &pgm, uint32_t &resume, double &fx,
+                                           double &fy) {
+    uint64_t sv;
+    double g, a, b, c, e;
+    asm volatile(
+        "s_and_saveexec_b64 %[sv], %[cm]\n\t"
+        "s_cbranch_execz .Lbh_carry_done_%=\n\t"
+        "v_mul_f64 %[g], %[Gm], %[mass]\n\t"  // (Config.G * b.m) * mass, BHA:256
+        "v_mov_b32 %[res], %[next]\n\t"
+        "s_cmp_lg_u64 %[om], 0\n\t"
+        "s_cbranch_scc1 .Lbh_carry_park_%=\n\t"
+        "s_cmp_lg_u64 %[pend], 0\n\t"
+        "s_cbranch_scc1 .Lbh_carry_take_%=\n"
+        ".Lbh_carry_block_%=:\n\t"
+        "v_rsq_f64 %[a], %[d2]\n\t"
+        "s_nop 0\n\t"
+        "v_mul_f64 %[b], %[d2], %[a]\n\t"
+        "v_mul_f64 %[a], %[a], 0.5\n\t"
+        "v_fma_f64 %[c], -%[a], %[b], 0.5\n\t"
+        "v_fmac_f64 %[b], %[b], %[c]\n\t"
+        "v_fmac_f64 %[a], %[a], %[c]\n\t"
+        "v_fma_f64 %[c], -%[b], %[b], %[d2]\n\t"
+        "v_fmac_f64 %[b], %[c], %[a]\n\t"
+        "v_fma_f64 %[c], -%[b], %[b], %[d2]\n\t"
+        "v_add_f64 %[e], %[a], %[a]\n\t"
+        "v_fmac_f64 %[b], %[c], %[a]\n\t"  // b = sqrt(d2)
+        "v_fma_f64 %[a], -%[b], %[e], 1.0\n\t"
+        "v_fmac_f64 %[e], %[e], %[a]\n\t"
+        "v_fma_f64 %[a], -%[b], %[e], 1.0\n\t"
+        "v_fmac_f64 %[e], %[a], %[e]\n\t"  // e = invR
+        "v_mul_f64 %[a], %[e], %[e]\n\t"
+        "v_fma_f64 %[b], -%[d2], %[a], 1.0\n\t"
+        "v_fmac_f64 %[a], %[a], %[b]\n\t"
+        "v_fma_f64 %[d2], -%[d2], %[a], 1.0\n\t"
+        "v_fmac_f64 %[a], %[d2], %[a]\n\t"  // a = invR2
+        "v_mul_f64 %[g], %[g], %[a]\n\t"    // f
+        "v_mul_f64 %[dx], %[dx], %[g]\n\t"
+        "v_mul_f64 %[dy], %[dy], %[g]\n\t"
+        "v_mul_f64 %[dx], %[e], %[dx]\n\t"
+        "v_mul_f64 %[dy], %[e], %[dy]\n\t"
+        "v_add_f64 %[fx], %[fx], %[dx]\n\t"
+        "v_add_f64 %[fy], %[fy], %[dy]\n\t"
+        "s_branch .Lbh_carry_done_%=\n"
+        ".Lbh_carry_park_%=:\n\t"  // a mixed stop: the accepting lanes' terms wait
+        "v_mov_b64 %[pdx], %[dx]\n\t"
+        "v_mov_b64 %[pdy], %[dy]\n\t"
+        "v_mov_b64 %[pd2], %[d2]\n\t"
+        "v_mov_b64 %[pgm], %[g]\n\t"
+        "s_or_b64 %[pend], %[pend], %[cm]\n\t"
+        "s_branch .Lbh_carry_done_%=\n"
+        ".Lbh_carry_take_%=:\n\t"  // the waiting lanes join this block on their own operands
+        "s_mov_b64 exec, %[pend]\n\t"
+        "v_mov_b64 %[dx], %[pdx]\n\t"
+        "v_mov_b64 %[dy], %[pdy]\n\t"
+        "v_mov_b64 %[d2], %[pd2]\n\t"
+        "v_mov_b64 %[g], %[pgm]\n\t"
+        "s_or_b64 exec, %[cm], %[pend]\n\t"
+        "s_mov_b64 %[pend], 0\n\t"
+        "s_branch .Lbh_carry_block_%=\n"
+        ".Lbh_carry_done_%=:\n\t"
+        "s_mov_b64 exec, %[sv]"
+        : [sv] "=&s"(sv), [pend] "+s"(pend), [g] "=&v"(g), [a] "=&v"(a), [b] "=&v"(b),
+          [c] "=&v"(c), [e] "=&v"(e), [dx] "+v"(dx), [dy] "+v"(dy), [d2] "+v"(d2),
+          [pdx] "+v"(pdx), [pdy] "+v"(pdy), [pd2] "+v"(pd2), [pgm] "+v"(pgm),
+          [res] "+v"(resume), [fx] "+v"(fx), [fy] "+v"(fy)
+        : [cm] "s"(cm), [om] "s"(om), [Gm] "v"(Gm), [mass] "s"(mass), [next] "s"(next)
+        : "scc");
+}
+
 template <bool FAST, bool COUNT, bool OFF32, bool POT = false>
 __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T, double bx,
                                      double by, double Gm, double soft2, double theta2,
@@ -50,6 +150,20 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
     // term is an exact +-0 (mass 0, finite f), and a massless internal node carries the leaf
     // flag too (bh_device.hpp NODE_SKIP), so the wave never descends below it -- only the
     // visit-counting variant must skip it.
+    constexpr bool CARRY = FAST && !POT;
+    uint64_t pend_m = 0;                              // lanes whose term waits (an SGPR pair)
+    double pdx = 0.0, pdy = 0.0, pd2 = 0.0, pgm = 0.0;  // their dx, dy, d2, Gm * mass
+    // BHA:250-259 from the square root on, order as written, for the lanes that run it
+    const auto fast_block = [&](double dx, double dy, double d2, double gmm)
+                                __attribute__((always_inline)) {
+        double h;
+        const double r = sqrt_rn_inrange_h(d2, h);
+        const double invR = rcp_rn_seeded(r, h + h);
+        const double invR2 = rcp_rn_seeded(d2, invR * invR);
+        const double f = gmm * invR2;
+        fx += f * dx * invR;
+        fy += f * dy * invR;
+    };
     cursor_walk<OFF32, !FAST || COUNT>(nodes, T, [&](const CursorStop<OFF32> &st)
                                                      __attribute__((always_inline)) {
         const double comX = st.comX, comY = st.comY, mass = st.mass;
@@ -101,7 +215,13 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
         if (COUNT) {  // contributions in the reference's sense: the own leaf is not one
             const bool own = (meta & NODE_LEAF) && (meta & NODE_BODY_MASK) == self;
             ncontrib += (__builtin_amdgcn_inverse_ballot_w64(contrib_m) && !own) ? 1u : 0u;
-            nblocks += contrib_m != 0ull ? 1u : 0u;
+            if (!CARRY) nblocks += contrib_m != 0ull ? 1u : 0u;
+        }
+        if (CARRY) {
+            carry_stop(contrib_m, open_m, pend_m, Gm, mass, next, dx, dy, d2, pdx, pdy, pd2, pgm,
+                       resume, fx, fy);
+            if (COUNT) nblocks += (contrib_m != 0ull && open_m == 0ull) ? 1u : 0u;
+            return ncur;
         }
         if (__builtin_amdgcn_inverse_ballot_w64(contrib_m)) {  // BHA:250-259, order as written
             double invR, invR2;
@@ -126,6 +246,10 @@ __device__ __forceinline__ void walk(const Node *__restrict__ nodes, uint32_t T,
         }
         return ncur;
     });
+    if (CARRY && pend_m != 0ull) {  // (no term waits at the end of a walk: free per stop)
+        if (__builtin_amdgcn_inverse_ballot_w64(pend_m)) fast_block(pdx, pdy, pd2, pgm);
+        if (COUNT) nblocks += 1;
+    }
 }
 
 
